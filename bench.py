@@ -302,6 +302,22 @@ with open(out, "a", buffering=1) as o:
                 "sclk_MHz_min": round(min(sclk), 1) if sclk else None, "mclk_MHz_avg": avg(mclk), "temp_C_avg": avg(temp)}
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, budget):
+    """Each device tensor as float32 `out_dir/<name>.npy`.  One larger than `budget` bytes is replaced by its flattened elements at a
+    fixed seeded set of positions (sorted, at most budget / 4 of them), which depends only on the element count: two runs with the
+    same arguments dump the same positions, so their files compare element for element."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.detach()
+        if a.numel() * 4 > budget:
+            idx = np.unique(np.random.default_rng(0).integers(0, a.numel(), budget // 4))
+            a = a.reshape(-1)[torch.from_numpy(idx).to(a.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), a.float().cpu().numpy())
+
+
 def load_fixture(name):
     path = os.path.join(GOLD, name)
     if not os.path.exists(path):
@@ -426,6 +442,9 @@ def main():
     ap.add_argument("--steps-only", action="store_true",
                     help="skip the extra passes and the parity leg: every launch then belongs to a stylise step, so a rocprofv3 "
                          "--stats summary of the run averages the same launch mix as `roofline`")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step returned to DIR/output.npy (N > 1: DIR/output_rank<r>.npy, each rank its strip), "
+                         "float32; beyond %d MB in all, a fixed seeded sample of its elements" % (DUMP_BUDGET_BYTES >> 20))
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -618,7 +637,7 @@ def main():
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             dt = float(tt.item())
         assert bool(torch.isfinite(res).all())
-        return dt
+        return dt, res
 
     def kernel_profile(eng, step, nprof=2, record=True):
         """HIP events around every kernel launch on the context's stream, overlap off so one event pair times one launch.
@@ -678,7 +697,9 @@ def main():
         step()
     if tele:
         tele.start()
-    dt = timed(step, args.steps, 0)
+    dt, last = timed(step, args.steps, 0)
+    # the one-rank step returns its reused `out` buffer: keep a device copy now, write it once the sustained block and telemetry are done
+    last = last.clone() if args.dump_outputs else None
     value = mp * args.steps / dt
 
     def sustained_block(seconds=2.0, n_fit=60):
@@ -690,7 +711,7 @@ def main():
         n = max(args.steps, int(seconds / max(dt / args.steps, 1e-4)))
         for _ in range(n):
             step()
-        dts = timed(step, args.steps, 0)
+        dts, _ = timed(step, args.steps, 0)
         res = {"ms_per_step_sustained": round(dts / args.steps * 1e3, 3), "after_s_of_back_to_back_steps": round(n * dt / args.steps, 2)}
         pts = []
         for _ in range(n_fit):
@@ -719,6 +740,9 @@ def main():
 
     sustained = sustained_block() if not args.steps_only else None
     telemetry = tele.stop() if tele else None
+    if last is not None:
+        dump_outputs(args.dump_outputs, {"output" if world == 1 else "output_rank%d" % rank: last}, DUMP_BUDGET_BYTES // world)
+    del last
     saturated = wct.saturation_count()      # threads that clamped an activation to the f16x3 range during the timed steps
     lat_med, lat_min, lat_max = latency_median(step, max(10, min(args.steps, 20)))
 
@@ -756,7 +780,7 @@ def main():
         del content
         step4, mp4, desc4, content4 = make_step("cfg4", wct)
         k4 = max(3, args.steps // 2)
-        dt4 = timed(step4, k4, 2)
+        dt4, _ = timed(step4, k4, 2)
         passes["cfg4_strong"] = {"workload": desc4, "ms_per_frame": round(dt4 / k4 * 1e3, 3), "MPs": round(mp4 * k4 / dt4, 1), "scaling": "strong",
                                  "collectives": collectives_used[0], "strips_vs_untiled_same_gpu": sharded_vs_untiled(step4.runner, content4, "cfg4", W4)}
         del step4, content4

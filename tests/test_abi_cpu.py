@@ -105,19 +105,30 @@ def test_debug_environment_is_gated():
     assert raw == [], raw
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/trained_models/wct_se_16x_new"), reason="the reference checkout exists in the build container only")
-def test_weights_only_loader_reads_the_reference_checkpoints():
-    """wct_hip.wct._load_state un-pickles with weights_only=True (no arbitrary code from a checkpoint).  The reference's real files
-    -- {"epoch", "model": state_dict} for the encoders (with the unused conv{k}1_aux heads), bare or wrapped state_dicts for the
-    decoders (model_cd.py:712-718) -- must load that way, without WCT_ALLOW_UNSAFE_PICKLE, and equal the packaged blob that
-    tools/make_goldens.py converted from them."""
+def test_weights_only_loader_reads_the_reference_checkpoints(tmp_path):
+    """wct_hip.wct._load_state un-pickles with weights_only=True (no arbitrary code from a checkpoint).  Files in the reference's
+    own on-disk layout -- torch's legacy (pre-zip) serialization of {"epoch", "model": OrderedDict} for all ten modules, the
+    encoders with their unused conv{j}1_aux heads (j <= k; model_cd.py:712-718) -- written here from the packaged blob, must load
+    that way, without WCT_ALLOW_UNSAFE_PICKLE, into exactly the blob's tensors (aux heads aside)."""
+    import collections
+    import zipfile
+    import torch
     from wct_hip import model_zoo
     from wct_hip.wct import _load_state
     blob = model_zoo.load_npz_weights(os.path.join(PKG, "weights", "16x.npz"))
     assert os.environ.get("WCT_ALLOW_UNSAFE_PICKLE") != "1"
+    rng = np.random.default_rng(3)
+    aux = {1: (64, 16), 2: (128, 32), 3: (256, 64), 4: (512, 128), 5: (512, 128)}
     for k in range(1, 6):
-        for key, path in (("e%d" % k, "/root/reference/trained_models/wct_se_16x_new/%dSE.pth" % k),
-                          ("d%d" % k, "/root/reference/trained_models/wct_se_16x_new_sd/%dSD.pth" % k)):
+        for key in ("e%d" % k, "d%d" % k):
+            sd = collections.OrderedDict((n[len(key) + 1:], torch.from_numpy(v.copy())) for n, v in blob.items() if n.startswith(key + "."))
+            for j in range(1, k + 1) if key[0] == "e" else ():
+                co, ci = aux[j] if (k, j) != (1, 1) else (64, 24)
+                sd["conv%d1_aux.weight" % j] = torch.from_numpy(rng.standard_normal((co, ci, 1, 1), dtype=np.float32))
+                sd["conv%d1_aux.bias" % j] = torch.from_numpy(rng.standard_normal(co, dtype=np.float32))
+            path = str(tmp_path / ("%d%s.pth" % (k, "SE" if key[0] == "e" else "SD")))
+            torch.save({"epoch": 20, "model": sd}, path, _use_new_zipfile_serialization=False)
+            assert not zipfile.is_zipfile(path)
             sd = _load_state(path)
             mine = {n[len(key) + 1:]: v for n, v in blob.items() if n.startswith(key + ".")}
             assert set(mine) <= set(sd) and all("aux" in n for n in set(sd) - set(mine)), key

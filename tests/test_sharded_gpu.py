@@ -36,8 +36,9 @@ def _shard_worker(rank, world, port, H, W, halo_mode, bmap, out_path, style_hw=(
     if backend == "nccl":            # one device per rank: RCCL over xGMI (only on a box with >= `world` devices)
         torch.cuda.set_device(rank)
         dist.init_process_group("nccl", rank=rank, world_size=world, device_id=torch.device("cuda", rank))
-    else:
-        dist.init_process_group("gloo", rank=rank, world_size=world)   # the ranks share the one GPU of the test box
+    else:                            # the ranks share the one GPU of the test box, at most four processes holding it (run_ranks)
+        from tools.sharded_standins import GlooRank
+        dist = GlooRank(rank, world, port)
     try:
         from wct_hip import WCT, model_zoo
         from wct_hip.sharded import ShardedStylizer
@@ -83,9 +84,9 @@ def test_sharded_ranks_match_untiled(tmp_path, world, H, W, halo_mode, bmap, smo
     untiled HIP cascade.  Not bitwise: the runs' (M, b) differ by ~1e-13 (moment summation order), which flips fp32 roundings
     of the folded decoder weights at level 5, and the cascade amplifies that level by level (tools/debug/shard_diag.py); the
     strips themselves are bit-exact given the same (M, b) (test_strip_halos_exact_per_level)."""
-    import torch.multiprocessing as mp
+    from tools import sharded_standins as standins
     out = str(tmp_path / "sh.npz")
-    mp.spawn(_shard_worker, args=(world, _free_port(), H, W, halo_mode, bmap, out, (300, 260), "rand", "gloo", False, smode), nprocs=world, join=True)
+    standins.run_ranks(_shard_worker, world, (world, _free_port(), H, W, halo_mode, bmap, out, (300, 260), "rand", "gloo", False, smode))
     z = np.load(out)
     assert z["got"].shape == z["ref"].shape == (1, 3, H // 16 * 16, W // 16 * 16)
     assert all(m == ("exchange" if halo_mode == "auto" else halo_mode) for m in z["modes"])
@@ -132,9 +133,8 @@ def test_device_buffer_collectives_are_checked(tmp_path, world, H, W, halo_mode,
         else:
             assert grp.calls["broadcast"] == (5 if bmap else 0)
     if world == 2:
-        import torch.multiprocessing as mp
         out = str(tmp_path / "sh.npz")
-        mp.spawn(_shard_worker, args=(world, _free_port(), H, W, halo_mode, bmap, out, (300, 260), "rand", "gloo", False, smode), nprocs=world, join=True)
+        standins.run_ranks(_shard_worker, world, (world, _free_port(), H, W, halo_mode, bmap, out, (300, 260), "rand", "gloo", False, smode))
         assert np.array_equal(np.load(out)["got"], got.cpu().numpy())
 
 
@@ -175,13 +175,14 @@ def test_c_cascade_bitwise_equals_python_orchestration(world, H, W, halo_mode, b
                                                             (8, 96, 2560, "exchange", False, "owner")])
 def test_c_cascade_multi_process_equals_python_orchestration(tmp_path, world, H, W, halo_mode, bmap, smode):
     """The library's cascade in a MULTI-PROCESS job (one process per rank, as deployed; here the ranks share the one GPU and the library's transport
-    table is the torch.distributed adapter over gloo, host-staged): bitwise the Python orchestration of the same job over the same process group
-    (gloo sums the ranks' terms in one order for both), selftest included -- 3, 4 and 8 ranks, neighbour exchange, (M, b) broadcast, style strips."""
-    import torch.multiprocessing as mp
+    table is the torch.distributed adapter over gloo, host-staged; 8 ranks run as 4 processes x 2 threads): bitwise the Python orchestration of the
+    same job over the same process group (gloo sums the ranks' terms in one order for both), selftest included -- 3, 4 and 8 ranks, neighbour exchange,
+    (M, b) broadcast, style strips."""
+    from tools import sharded_standins as standins
     outs = []
     for c_cascade in (False, True):
         out = str(tmp_path / ("c%d.npz" % c_cascade))
-        mp.spawn(_shard_worker, args=(world, _free_port(), H, W, halo_mode, bmap, out, (200, 333), "rand", "gloo", False, smode, c_cascade), nprocs=world, join=True)
+        standins.run_ranks(_shard_worker, world, (world, _free_port(), H, W, halo_mode, bmap, out, (200, 333), "rand", "gloo", False, smode, c_cascade))
         outs.append(np.load(out))
     assert np.array_equal(outs[0]["got"], outs[1]["got"])
     assert rel_err(outs[1]["got"], outs[1]["ref"]) < 5e-4
@@ -278,9 +279,9 @@ def test_config4_eight_strips_match_untiled(tmp_path):
     ranks (here sharing the one GPU over gloo; on the 8-GPU node: RCCL), halo mode "auto" = neighbour exchange at this strip
     width, style statistics computed once per node and broadcast, all-reduced moments -- against the untiled single-GPU
     cascade of the same frame."""
-    import torch.multiprocessing as mp
+    from tools import sharded_standins as standins
     out = str(tmp_path / "sh8.npz")
-    mp.spawn(_shard_worker, args=(8, _free_port(), 4096, 10240, "auto", False, out, (2048, 2048)), nprocs=8, join=True)
+    standins.run_ranks(_shard_worker, 8, (8, _free_port(), 4096, 10240, "auto", False, out, (2048, 2048)))
     z = np.load(out)
     assert z["got"].shape == z["ref"].shape == (1, 3, 4096, 10240)
     assert all(m == "exchange" for m in z["modes"])
@@ -333,7 +334,6 @@ def test_config4_geometry_vs_reference(tmp_path, oracle):
       (c) the same job with every collective on DEVICE buffers (tools/sharded_standins.py InProcessWorld -- the branch RCCL takes);
     (b) and (c) must also agree with each other to fp32-rounding level (different summation orders of eight moment terms)."""
     import torch
-    import torch.multiprocessing as mp
     from tests.conftest import load_golden
     from tests.fixture_compare import GATE, cfg4_geometry_frames, compare_to_fixture
     from tools import sharded_standins as standins
@@ -350,7 +350,7 @@ def test_config4_geometry_vs_reference(tmp_path, oracle):
     assert eng.saturation_count() == 0
     ru = compare_to_fixture(untiled, g16)
     out = str(tmp_path / "g16.npz")
-    mp.spawn(_shard_worker, args=(8, _free_port(), 512, 10240, "auto", False, out, (2048, 2048), "g16", "gloo", False, "owner"), nprocs=8, join=True)
+    standins.run_ranks(_shard_worker, 8, (8, _free_port(), 512, 10240, "auto", False, out, (2048, 2048), "g16", "gloo", False, "owner"))
     z = np.load(out)
     assert all(m == "exchange" for m in z["modes"])
     rg = compare_to_fixture(z["got"][0], g16)
@@ -519,11 +519,9 @@ def _cfg5_worker(rank, world, port, out_dir):
             sys.path.insert(0, p)
     import hashlib
     import torch
-    import torch.distributed as dist
     from tests.fixture_compare import noise_frame
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
+    from tools.sharded_standins import GlooRank
+    dist = GlooRank(rank, world, port)
     try:
         from wct_hip import WCT, model_zoo
         from wct_hip.replicas import ReplicaStylizer
@@ -550,12 +548,12 @@ def test_config5_eight_4k_contents_one_style(tmp_path):
     result), and so does wct_hip/pipeline.py's FramePipeline with three of these frames in flight on one GPU."""
     import hashlib
     import torch
-    import torch.multiprocessing as mp
     from tests.fixture_compare import noise_frame
+    from tools import sharded_standins as standins
     from wct_hip import WCT, model_zoo
     from wct_hip.pipeline import FramePipeline
     world = 8
-    mp.spawn(_cfg5_worker, args=(world, _free_port(), str(tmp_path)), nprocs=world, join=True)
+    standins.run_ranks(_cfg5_worker, world, (world, _free_port(), str(tmp_path)))
     weights = model_zoo.load_npz_weights(os.path.join(PKG, "weights", "16x.npz"))
     make = lambda: WCT(types.SimpleNamespace(mode="16x", alpha=1.0), weights=weights)   # noqa: E731
     wct = make()
@@ -568,7 +566,7 @@ def test_config5_eight_4k_contents_one_style(tmp_path):
     aborts = [open(str(tmp_path / ("r%d.aborts" % r))).read() for r in range(world)]
     print("\n[cfg5] single-launch solves aborted / enqueued per rank:", aborts)
     # Bitwise -- unless a rank's single-launch matrix-function solve ABORTED into the Jacobi net (include/wct_hip.h wct_debug_get "nscoop_aborts"):
-    # eight PROCESSES share this one GPU here, a solve's 32 workgroups must all be resident on one XCD while seven other processes' persistent
+    # eight RANKS share this one GPU here, a solve's 32 workgroups must all be resident on one XCD while seven other ranks' persistent
     # kernels hold CUs, and now and then (round 6: 4 of ~260 process runs, tools/debug/cfg5_stress.py) the 5 ms watchdog fires first.  The repaired
     # solve is correct but not bit-identical (measured 5.6e-6 / 6.8e-6 of the image's maximum after the cascade).  So: no abort -> equal hashes;
     # an abort on that rank -> within 5e-5 on the 1/256 lattice the worker kept.  One process per GPU (the product's deployment) never aborts.
@@ -683,20 +681,37 @@ needs_two_devices = pytest.mark.skipif(_n_devices() < 2, reason="needs >= 2 MI35
                                                                 "collected everywhere, runs the day a multi-GPU node runs this suite")
 
 
-@needs_two_devices
+def _two_rank_job(record_property, out, halo_mode, bmap, c_coll=False, smode="auto", c_cascade=False):
+    """The 2-rank 272 x 1525 job of the tests below: one DEVICE per rank over torch.distributed "nccl" (= RCCL; the library's own table for
+    c_coll / c_cascade) where there are two devices.  RCCL refuses two ranks on one device ("Duplicate GPU detected"), so on a one-device
+    box the same two processes share it over gloo (the library's collectives through the torch.distributed adapter): the sharding, the
+    library's level / cascade calls and the bitwise comparisons run, RCCL and xGMI do NOT -- a pass there says nothing about them (the
+    *_single_rank tests run RCCL at world 1).  The backend used is recorded on the test (property `dist_backend`) and printed."""
+    backend = "nccl" if _n_devices() >= 2 else "gloo"
+    record_property("dist_backend", backend)
+    args = (2, _free_port(), 272, 1525, halo_mode, bmap, out, (300, 260), "rand", backend, c_coll, smode, c_cascade)
+    if backend == "nccl":
+        import torch.multiprocessing as mp
+        mp.spawn(_shard_worker, args=args, nprocs=2, join=True)
+    else:
+        from tools import sharded_standins as standins
+        standins.run_ranks(_shard_worker, 2, args)
+    print("\n[2-rank job] torch.distributed backend: %s%s" % (backend, "" if backend == "nccl" else " (one device: RCCL / xGMI not exercised)"))
+
+
 @pytest.mark.parametrize("halo_mode,bmap", [("exchange", False), ("recompute", False), ("exchange", True), ("recompute", True)])
-def test_two_devices_rccl_matches_untiled_and_in_process(tmp_path, halo_mode, bmap):
-    """FIRST CONTACT WITH xGMI (VERDICT r4 task 2): the 2-rank job with one DEVICE per rank over torch.distributed "nccl" (= RCCL) --
+def test_two_devices_rccl_matches_untiled_and_in_process(tmp_path, record_property, halo_mode, bmap):
+    """On two devices, FIRST CONTACT WITH xGMI (VERDICT r4 task 2); on one device the same assertions over gloo, without RCCL (_two_rank_job).
+    The 2-rank job with one DEVICE per rank over torch.distributed "nccl" (= RCCL) --
     moments all-reduce, style-statistics / (M, b) broadcasts, neighbour exchange or recomputed halos, both map arrangements -- against
     the untiled cascade (the gloo test's tolerance) and BITWISE against the same job on InProcessWorld's device-buffer collectives (a
     two-term sum is commutative: every transport must agree to the last bit)."""
     import torch
-    import torch.multiprocessing as mp
     from tools import sharded_standins as standins
     from wct_hip import WCT, model_zoo
     world, H, W = 2, 272, 1525
     out = str(tmp_path / "sh.npz")
-    mp.spawn(_shard_worker, args=(world, _free_port(), H, W, halo_mode, bmap, out, (300, 260), "rand", "nccl"), nprocs=world, join=True)
+    _two_rank_job(record_property, out, halo_mode, bmap)
     z = np.load(out)
     assert z["got"].shape == z["ref"].shape == (1, 3, H // 16 * 16, W // 16 * 16)
     assert rel_err(z["got"], z["ref"]) < 5e-4
@@ -764,29 +779,29 @@ print('CCOLL_OK %%.2e' %% err)
     assert r.returncode == 0 and "CCOLL_OK" in r.stdout, (r.stdout[-1500:], r.stderr[-3000:])
 
 
-@needs_two_devices
 @pytest.mark.parametrize("halo_mode", ["exchange", "recompute"])
-def test_two_devices_c_collectives_bitwise_equal_torch_distributed(tmp_path, halo_mode):
-    """Two devices: the library's own all-reduce (wct_level_sharded over xGMI) against torch.distributed's, same job, bit for bit."""
-    import torch.multiprocessing as mp
+def test_two_devices_c_collectives_bitwise_equal_torch_distributed(tmp_path, record_property, halo_mode):
+    """Two devices: the library's own all-reduce (wct_level_sharded over xGMI) against torch.distributed's, same job, bit for bit.  One
+    device, without RCCL (_two_rank_job): wct_level_sharded's all-reduce through the torch.distributed adapter over gloo in a multi-process
+    job, against torch.distributed's, bit for bit (no other test runs the per-level library call across processes)."""
     outs = []
     for c_coll in (False, True):
         out = str(tmp_path / ("c%d.npz" % c_coll))
-        mp.spawn(_shard_worker, args=(2, _free_port(), 272, 1525, halo_mode, False, out, (300, 260), "rand", "nccl", c_coll), nprocs=2, join=True)
+        _two_rank_job(record_property, out, halo_mode, False, c_coll=c_coll)
         outs.append(np.load(out)["got"])
     assert np.array_equal(outs[0], outs[1])
 
 
-@needs_two_devices
 @pytest.mark.parametrize("halo_mode,bmap,smode", [("exchange", False, "strips"), ("recompute", False, "strips"), ("exchange", True, "owner"), ("recompute", False, "owner")])
-def test_two_devices_c_cascade_bitwise_equal_torch_distributed(tmp_path, halo_mode, bmap, smode):
+def test_two_devices_c_cascade_bitwise_equal_torch_distributed(tmp_path, record_property, halo_mode, bmap, smode):
     """Two devices: the whole cascade as ONE library call per rank (wct_stylize_sharded: ncclAllReduce / ncclBroadcast / grouped ncclSend +
-    ncclRecv issued by the library over xGMI, after wct_comm_selftest) against wct_hip/sharded.py over torch.distributed, bit for bit."""
-    import torch.multiprocessing as mp
+    ncclRecv issued by the library over xGMI, after wct_comm_selftest) against wct_hip/sharded.py over torch.distributed, bit for bit.  One
+    device, without RCCL (_two_rank_job): the same call with the torch.distributed adapter over gloo as its transport table, at the world
+    of two edge strips that the 3 / 4 / 8-rank test_c_cascade_multi_process_equals_python_orchestration does not cut."""
     outs = []
     for c_cascade in (False, True):
         out = str(tmp_path / ("c%d.npz" % c_cascade))
-        mp.spawn(_shard_worker, args=(2, _free_port(), 272, 1525, halo_mode, bmap, out, (300, 260), "rand", "nccl", False, smode, c_cascade), nprocs=2, join=True)
+        _two_rank_job(record_property, out, halo_mode, bmap, smode=smode, c_cascade=c_cascade)
         outs.append(np.load(out)["got"])
     assert np.array_equal(outs[0], outs[1])
 

@@ -145,6 +145,102 @@ def dist_transport(dist):
     return guard(all_reduce), guard(broadcast), guard(sendrecv)
 
 
+class GlooRank:
+    """ONE rank of a `world`-rank gloo job as an object with torch.distributed's call surface (the subset wct_hip.sharded,
+    wct_hip.replicas, dist_transport and the test workers use): its own TCPStore client and ProcessGroupGloo instead of the
+    process-wide default group, so that one process can host several ranks as threads (run_ranks).  The collectives are gloo's,
+    exactly as under dist.init_process_group("gloo"); only the number of processes changes."""
+
+    isend, irecv = "isend", "irecv"
+
+    def __init__(self, rank: int, world: int, port: int, timeout_s: float = 900.0):
+        import datetime
+        import torch.distributed as dist
+        timeout = datetime.timedelta(seconds=timeout_s)
+        self.rank, self.world, self._dist = rank, world, dist
+        self.store = dist.TCPStore("127.0.0.1", port, world, rank == 0, timeout)
+        self.pg = dist.ProcessGroupGloo(self.store, rank, world, timeout)
+
+    def get_rank(self):
+        return self.rank
+
+    def get_world_size(self):
+        return self.world
+
+    def get_backend(self):
+        return "gloo"
+
+    def all_reduce(self, t, op=None):
+        assert op is None or op == self._dist.ReduceOp.SUM
+        self.pg.allreduce([t]).wait()
+
+    def broadcast(self, t, src=0):
+        opts = self._dist.BroadcastOptions()
+        opts.rootRank = src
+        self.pg.broadcast([t], opts).wait()
+
+    @staticmethod
+    def P2POp(kind, tensor, peer):
+        return kind, tensor, peer
+
+    def batch_isend_irecv(self, ops):
+        return [self.pg.send([t], peer, 0) if kind == self.isend else self.pg.recv([t], peer, 0) for kind, t, peer in ops]
+
+    def all_gather_object(self, out, obj):
+        import pickle
+        data = torch.frombuffer(bytearray(pickle.dumps(obj)), dtype=torch.uint8)
+        sizes = [torch.zeros(1, dtype=torch.int64) for _ in range(self.world)]
+        self.pg.allgather([sizes], [torch.tensor([data.numel()], dtype=torch.int64)]).wait()
+        buf = torch.zeros(int(max(s.item() for s in sizes)), dtype=torch.uint8)
+        buf[:data.numel()] = data
+        bufs = [torch.empty_like(buf) for _ in range(self.world)]
+        self.pg.allgather([bufs], [buf]).wait()
+        for i in range(self.world):
+            out[i] = pickle.loads(bufs[i][:int(sizes[i].item())].numpy().tobytes())
+
+    def barrier(self):
+        self.pg.barrier().wait()
+
+    def destroy_process_group(self):
+        self.pg = self.store = None
+
+
+def run_ranks(fn, world: int, args=(), max_procs: int = 4):
+    """fn(rank, *args) for every rank of a `world`-rank job, hosted by at most `max_procs` processes (contiguous blocks of ranks,
+    the ranks of one process as threads, each on a stream of its own when it uses the GPU).  The ranks of a one-GPU job each hold
+    the device, and a shared box caps how many processes may hold it at once, so an 8-rank job runs as 4 processes x 2 ranks."""
+    import torch.multiprocessing as mp
+    procs = min(world, max_procs)
+    mp.spawn(_rank_host, args=(fn, world, procs, tuple(args)), nprocs=procs, join=True)
+
+
+def _rank_host(p, fn, world, procs, args):
+    ranks = [r for r in range(world) if r * procs // world == p]
+    if len(ranks) == 1:
+        fn(ranks[0], *args)
+        return
+    import threading
+    import traceback
+
+    def work(r):
+        try:
+            if torch.cuda.is_available():
+                with torch.cuda.stream(torch.cuda.Stream()):
+                    fn(r, *args)
+            else:
+                fn(r, *args)
+        except BaseException:      # noqa: BLE001  its peers would wait in a collective until the timeout: end the process now
+            traceback.print_exc()
+            sys.stderr.flush()
+            os._exit(1)
+
+    threads = [threading.Thread(target=work, args=(r,)) for r in ranks]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join()
+
+
 class InProcessWorld:
     """ALL ranks of a `world`-rank job as threads of ONE process on ONE device, each with its own engine and its own stream --
     a stand-in for RCCL whose collectives move DEVICE buffers and are ordered by events only (no host staging, no stream or
