@@ -140,6 +140,11 @@ struct wct_ctx {
   bool prof = false;
   std::vector<ProfRec> recs;
   std::map<std::string, wct_prof_entry> prof_acc;
+  // spatial control (wct_stylize_regions, wct_moments_labeled, wct_apply_labeled): K style slots per level (cov_s^(1/2), mu_s), the
+  // regions' content results, the level label maps, per-label moments [n K | sum K*C | sumsq K*C*C], the K maps [M K*C*C | b K*C],
+  // the transformed feature map, the kernels' workspaces; pinned [6][256] label histograms read back once per call
+  DevBuf eigR[8][6], eigCR[8], regLab, regHist, regSums, regMb, regFeat, wsRegMom, wsRegApply;
+  unsigned* reg_hist_host = nullptr;
 };
 
 // RCCL, resolved at run time (wct_comm_load): the library keeps no link-time dependency on it
@@ -1046,6 +1051,12 @@ void wct_destroy(wct_ctx* ctx) {
   if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
   if (ctx->ev_join) (void)hipEventDestroy(ctx->ev_join);
   for (DevBuf* b : {&ctx->shIn, &ctx->shOut, &ctx->shNext, &ctx->shEdge, &ctx->shStyle, &ctx->shStats, &ctx->shMb}) release(*b);
+  for (int k = 0; k < 8; ++k) {
+    for (int l = 0; l < 6; ++l) release(ctx->eigR[k][l]);
+    release(ctx->eigCR[k]);
+  }
+  for (DevBuf* b : {&ctx->regLab, &ctx->regHist, &ctx->regSums, &ctx->regMb, &ctx->regFeat, &ctx->wsRegMom, &ctx->wsRegApply}) release(*b);
+  if (ctx->reg_hist_host) (void)hipHostFree(ctx->reg_hist_host);
 
   if (ctx->side.stream) (void)hipStreamDestroy(ctx->side.stream);
   if (ctx->sat_dev) (void)hipFree(ctx->sat_dev);
@@ -1999,6 +2010,208 @@ int wct_profile_read(wct_ctx* ctx, wct_prof_entry* entries, int max_entries, int
   }
   *n_entries = n;
   return WCT_OK;
+}
+
+}  // extern "C"
+
+// =====================================================================================================
+// Spatial control: K styles over the regions of a uint8 label map (regions.hip).  Per region, the level's transform is the
+// reference's whiten_and_color (util_wct.py:62-131) on that region's feature columns; everything else in the cascade is local.
+namespace {
+constexpr int REG_MAX = 8;
+
+int labeled_args(wct_ctx* ctx, const char* what, int C, int h, int w, int K) {
+  if (C < 4 || (C & 3) || C > 512) return fail(ctx, WCT_ERR_INVALID, "%s: C=%d must be a multiple of 4 in [4,512]", what, C);
+  if (h < 1 || w < 1) return fail(ctx, WCT_ERR_INVALID, "%s: bad map %dx%d", what, h, w);
+  if (K < 1 || K > REG_MAX) return fail(ctx, WCT_ERR_INVALID, "%s: K=%d outside [1, %d]", what, K, REG_MAX);
+  return WCT_OK;
+}
+
+int moments_labeled_impl(wct_ctx* ctx, Lane& ln, const float* feat, int C, int h, int w, const uint8_t* lab, int K, double* n, double* sum,
+                         double* sumsq) {
+  const long npix = (long)h * w;
+  if (int rc = ensure(ctx, ctx->wsRegMom, moments_labeled_workspace_bytes(C, npix, K))) return rc;
+  ProfScope ps(ctx, ln.stream, "moments_labeled", 2.0 * C * C * npix, 4.0 * C * npix + (double)K * npix);
+  HIPCHK(ctx, launch_moments_labeled(feat, C, npix, lab, K, n, sum, sumsq, ctx->wsRegMom.p, ctx->wsRegMom.cap, ln.stream, mom32_on(ctx, npix)));
+  return WCT_OK;
+}
+
+int apply_labeled_impl(wct_ctx* ctx, const float* feat, int C, long npix, const uint8_t* lab, int K, const double* M, const double* b, float* out) {
+  if (int rc = ensure(ctx, ctx->wsRegApply, apply_labeled_workspace_bytes(C, K))) return rc;
+  ProfScope ps(ctx, ctx->main.stream, "apply_labeled", 2.0 * C * C * npix, 8.0 * C * npix + npix);
+  HIPCHK(ctx, launch_apply_labeled(feat, C, npix, lab, K, M, b, out, ctx->wsRegApply.p, ctx->wsRegApply.cap, ctx->main.stream));
+  return WCT_OK;
+}
+
+// style side of one level for style slot k (the same steps as style_side, into eigR[k][level]; no fold: the regions' maps are applied
+// to the features, not folded into the decoder)
+int style_side_slot(wct_ctx* ctx, int level, int k, const float* style, int Hs, int Ws) {
+  Module& me = ctx->mod[WCT_KIND_ENC][level];
+  if (!me.loaded) return fail(ctx, WCT_ERR_STATE, "encoder %d not loaded", level);
+  const int C = me.layers.back().d.cout;
+  int hs, ws;
+  level_dims(level, Hs, Ws, hs, ws);
+  Lane& ln = ctx->overlap ? ctx->side : ctx->main;
+  if (int rc = ensure(ctx, ctx->featS, (size_t)hs * ws * C * sizeof(float))) return rc;
+  SumsView sv;
+  if (int rc = sums_view(ctx, ln, sv)) return rc;
+  float* fS = reinterpret_cast<float*>(ctx->featS.p);
+  if (l1_fused(ctx, level)) {
+    if (int rc = l1_moments_impl(ctx, ln, level, style, Hs, Ws, 0, Ws, sv.sum, sv.sumsq)) return rc;
+  } else {
+    if (int rc = encode_impl(ctx, ln, level, style, Hs, Ws, fS, nullptr, nullptr)) return rc;
+    if (int rc = moments_impl(ctx, ln, fS, C, hs, ws, 0, ws, sv.sum, sv.sumsq)) return rc;
+  }
+  if (int rc = eig_impl(ctx, ln, C, (double)hs * ws, sv.sum, sv.sumsq, 0, ctx->eigR[k][level], sv.info + 1)) return rc;
+  HIPCHK(ctx, hipEventRecord(ctx->ev_style[level], ln.stream));
+  return WCT_OK;
+}
+
+// geometry of a regions call: level L's feature map is h[L] x w[L] in every run (the cascade crops to multiples of 16 at level 5 and
+// keeps that size), its label map lives at regLab + off[L]; cnt[L][v] = pixels of lab_L with label v (host, read back once)
+struct RegionPlan {
+  int h[6], w[6];
+  size_t off[6];
+  unsigned cnt[6][256];
+};
+
+// one level of the regions cascade on the main lane: encoder (fp32 NHWC) -> per-label moments -> one content solve per region with
+// >= 2 pixels, against style slot k -> per-label apply -> the decoder with its unfolded first conv
+int regions_level(wct_ctx* ctx, int level, const float* img, int H, int W, const RegionPlan& pl, int K, const float* alpha, float* dst) {
+  Module& me = ctx->mod[WCT_KIND_ENC][level];
+  const int C = me.layers.back().d.cout;
+  int h, w;
+  level_dims(level, H, W, h, w);
+  if (h != pl.h[level] || w != pl.w[level]) return fail(ctx, WCT_ERR_INVALID, "regions: level %d map %dx%d, planned %dx%d", level, h, w, pl.h[level], pl.w[level]);
+  Lane& ln = ctx->main;
+  const size_t fbytes = (size_t)h * w * C * sizeof(float), cc = (size_t)C * C;
+  if (int rc = ensure(ctx, ctx->featC, fbytes)) return rc;
+  if (int rc = ensure(ctx, ctx->regFeat, fbytes)) return rc;
+  if (int rc = ensure(ctx, ctx->regSums, (size_t)K * (1 + C + cc) * sizeof(double))) return rc;
+  if (int rc = ensure(ctx, ctx->regMb, (size_t)K * (cc + C) * sizeof(double))) return rc;
+  SumsView sv;
+  if (int rc = sums_view(ctx, ln, sv)) return rc;
+  float* fC = reinterpret_cast<float*>(ctx->featC.p);
+  float* fO = reinterpret_cast<float*>(ctx->regFeat.p);
+  double* n = reinterpret_cast<double*>(ctx->regSums.p);
+  double* sum = n + K;
+  double* sumsq = sum + (size_t)K * C;
+  double* M = reinterpret_cast<double*>(ctx->regMb.p);
+  double* b = M + (size_t)K * cc;
+  const uint8_t* lab = reinterpret_cast<const uint8_t*>(ctx->regLab.p) + pl.off[level];
+  if (int rc = encode_impl(ctx, ln, level, img, H, W, fC, nullptr, nullptr)) return rc;
+  if (int rc = moments_labeled_impl(ctx, ln, fC, C, h, w, lab, K, n, sum, sumsq)) return rc;
+  unsigned ident = 0;
+  for (int k = 0; k < K; ++k) {
+    const double nk = pl.cnt[level][k];
+    if (nk < 2) { ident |= 1u << k; continue; }
+    if (int rc = eig_impl(ctx, ln, C, nk, sum + (size_t)k * C, sumsq + k * cc, 1, ctx->eigCR[k], sv.info)) return rc;
+  }
+  HIPCHK(ctx, hipStreamWaitEvent(ln.stream, ctx->ev_style[level], 0));
+  for (int k = 0; k < K; ++k)
+    if (!(ident >> k & 1u))
+      if (int rc = assemble_impl(ctx, C, ctx->eigCR[k], ctx->eigR[k][level], alpha[k], M + k * cc, b + (size_t)k * C)) return rc;
+  HIPCHK(ctx, launch_mb_identity(M, b, C, K, ident, ln.stream));
+  if (int rc = apply_labeled_impl(ctx, fC, C, (long)h * w, lab, K, M, b, fO)) return rc;
+  return decode_impl(ctx, level, fO, h, w, nullptr, dst);
+}
+}  // namespace
+
+extern "C" {
+
+int wct_moments_labeled(wct_ctx* ctx, const float* feat, int C, int h, int w, const uint8_t* lab, int K, double* n, double* sum,
+                        double* sumsq) {
+  if (!ctx) return WCT_ERR_INVALID;
+  WCT_GUARD(ctx);
+  if (!feat || !lab || !n || !sum || !sumsq) return fail(ctx, WCT_ERR_INVALID, "moments_labeled: NULL pointer");
+  if (int rc = labeled_args(ctx, "moments_labeled", C, h, w, K)) return rc;
+  return moments_labeled_impl(ctx, ctx->main, feat, C, h, w, lab, K, n, sum, sumsq);
+}
+
+int wct_apply_labeled(wct_ctx* ctx, const float* feat, int C, int h, int w, int layout, const uint8_t* lab, int K, const double* M,
+                      const double* b, float* out) {
+  if (!ctx) return WCT_ERR_INVALID;
+  WCT_GUARD(ctx);
+  if (!feat || !lab || !M || !b || !out) return fail(ctx, WCT_ERR_INVALID, "apply_labeled: NULL pointer");
+  if (int rc = labeled_args(ctx, "apply_labeled", C, h, w, K)) return rc;
+  const long npix = (long)h * w;
+  if (layout == WCT_LAYOUT_NHWC) return apply_labeled_impl(ctx, feat, C, npix, lab, K, M, b, out);
+  if (layout != WCT_LAYOUT_NCHW) return fail(ctx, WCT_ERR_INVALID, "apply_labeled: bad layout %d", layout);
+  const size_t fbytes = (size_t)npix * C * sizeof(float);
+  if (int rc = ensure(ctx, ctx->tmpT, 2 * fbytes)) return rc;
+  float* t0 = reinterpret_cast<float*>(ctx->tmpT.p);
+  float* t1 = t0 + (size_t)npix * C;
+  HIPCHK(ctx, launch_nchw_to_nhwc(feat, t0, C, (int)npix, ctx->main.stream));
+  if (int rc = apply_labeled_impl(ctx, t0, C, npix, lab, K, M, b, t1)) return rc;
+  HIPCHK(ctx, launch_nhwc_to_nchw(t1, out, C, (int)npix, ctx->main.stream));
+  return WCT_OK;
+}
+
+int wct_stylize_regions(wct_ctx* ctx, const float* content, int H, int W, const uint8_t* labels, int K, const float* const* styles,
+                        const int* Hs, const int* Ws, const float* alpha, int num_run, float* out, int* Ho, int* Wo) {
+  if (!ctx) return WCT_ERR_INVALID;
+  WCT_GUARD(ctx);
+  if (!content || !labels || !styles || !Hs || !Ws || !alpha || !out || num_run < 1) return fail(ctx, WCT_ERR_INVALID, "stylize_regions: bad arguments");
+  if (K < 1 || K > REG_MAX) return fail(ctx, WCT_ERR_INVALID, "stylize_regions: K=%d outside [1, %d]", K, REG_MAX);
+  for (int k = 0; k < K; ++k) {
+    if (!styles[k]) return fail(ctx, WCT_ERR_INVALID, "stylize_regions: style %d is NULL", k);
+    if (!std::isfinite(alpha[k])) return fail(ctx, WCT_ERR_INVALID, "stylize_regions: alpha[%d] is not finite", k);
+  }
+  for (int level = 1; level <= 5; ++level)
+    if (!ctx->mod[WCT_KIND_ENC][level].loaded || !ctx->mod[WCT_KIND_DEC][level].loaded) return fail(ctx, WCT_ERR_STATE, "stylize_regions: level %d not loaded", level);
+  if (H < 32 || W < 32) return fail(ctx, WCT_ERR_INVALID, "stylize_regions: content %dx%d too small for level 5", H, W);
+  // label maps of the five levels + their histograms, read back ONCE: the solvers take each region's pixel count on the host, and the
+  // labels are checked before anything is written to `out`
+  RegionPlan pl{};
+  size_t total = 0;
+  for (int level = 5; level >= 1; --level) {
+    pl.h[level] = (H >> 4) << (5 - level);
+    pl.w[level] = (W >> 4) << (5 - level);
+    pl.off[level] = total;
+    total += ((size_t)pl.h[level] * pl.w[level] + 255) & ~(size_t)255;
+  }
+  if (int rc = ensure(ctx, ctx->regLab, total)) return rc;
+  if (int rc = ensure(ctx, ctx->regHist, 6 * 256 * sizeof(unsigned))) return rc;
+  if (!ctx->reg_hist_host) HIPCHK(ctx, hipHostMalloc(reinterpret_cast<void**>(&ctx->reg_hist_host), 6 * 256 * sizeof(unsigned), hipHostMallocDefault));
+  uint8_t* maps[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  for (int level = 1; level <= 5; ++level) maps[level] = reinterpret_cast<uint8_t*>(ctx->regLab.p) + pl.off[level];
+  unsigned* hist = reinterpret_cast<unsigned*>(ctx->regHist.p);
+  {
+    ProfScope ps(ctx, ctx->main.stream, "labels_levels", 0, (double)H * W + 2.0 * total);
+    HIPCHK(ctx, launch_labels_levels(labels, H, W, pl.h, pl.w, maps, hist, ctx->main.stream));
+  }
+  HIPCHK(ctx, hipMemcpyAsync(ctx->reg_hist_host, hist, 6 * 256 * sizeof(unsigned), hipMemcpyDeviceToHost, ctx->main.stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->main.stream));
+  memcpy(pl.cnt, ctx->reg_hist_host, sizeof pl.cnt);
+  for (int v = K; v < 255; ++v)
+    if (pl.cnt[0][v])
+      return fail(ctx, WCT_ERR_INVALID, "stylize_regions: label value %d (%u pixels) is neither a region 0..%d nor 255 (unstyled)", v, pl.cnt[0][v], K - 1);
+  if (int rc = with_deferred_solves(ctx, false, [&]() -> int {
+        if (int rc = fork_side(ctx)) return rc;
+        for (int k = 0; k < K; ++k)
+          if (int rc = style_side_slot(ctx, 5, k, styles[k], Hs[k], Ws[k])) return rc;
+        // as cascade(): `out` doubles as the running image; the style slots of level L - 1 are enqueued behind level L's content side
+        const size_t img_bytes = (size_t)3 * H * W * sizeof(float);
+        if (int rc = ensure(ctx, ctx->tmpT, img_bytes)) return rc;
+        float* bufs[2] = {reinterpret_cast<float*>(ctx->tmpT.p), out};
+        const float* cur = content;
+        int h = H, w = W, which = (5 * num_run) & 1;
+        for (int run = 0; run < num_run; ++run)
+          for (int level = 5; level >= 1; --level) {
+            float* dst = bufs[which];
+            if (int rc = regions_level(ctx, level, cur, h, w, pl, K, alpha, dst)) return rc;
+            if (run == 0 && level > 1)
+              for (int k = 0; k < K; ++k)
+                if (int rc = style_side_slot(ctx, level - 1, k, styles[k], Hs[k], Ws[k])) return rc;
+            h = pl.h[level] << (level - 1); w = pl.w[level] << (level - 1);
+            cur = dst; which ^= 1;
+          }
+        if (cur != out) HIPCHK(ctx, hipMemcpyAsync(out, cur, (size_t)3 * h * w * sizeof(float), hipMemcpyDeviceToDevice, ctx->main.stream));
+        if (Ho) *Ho = h;
+        if (Wo) *Wo = w;
+        return WCT_OK;
+      })) return rc;
+  return range_readback(ctx);
 }
 
 }  // extern "C"

@@ -191,3 +191,19 @@ hipError_t launch_fold_fast(const float* w_oihw, const float* bias, int cout, in
 // pack [cout][cin][3][3] (+ bias) into the conv kernel's layout (device side, used for the apply conv)
 hipError_t launch_pack_center_tap(const double* M, const double* b, int C, int cout_pad, float* wpk_out,
                                   float* bias_out, hipStream_t s);
+
+// ---- spatial control (regions.hip): per-label moments and affine maps over a uint8 label map (label >= K: unstyled)
+//   launch_labels_levels  lab_L[i][j] = labels[i s + s/2][j s + s/2] (s = 2^(L-1)) into out[L] (h[L] x w[L], L = 1..5) and the
+//                         histograms hist[6][256] (device, zeroed here): [0] = the whole H x W map, [L] = lab_L
+//   launch_moments_labeled  n[K], sum[K][C], sumsq[K][C][C] (fp64) of an NHWC map of npix pixels; f32_products as launch_moments
+//   launch_apply_labeled    out_p = M_lab(p) x_p + b_lab(p) (fp64 maps used in fp32), labels >= K copied through
+//   launch_mb_identity      M_k = I, b_k = 0 for the labels set in `mask`
+hipError_t launch_labels_levels(const uint8_t* labels, int H, int W, const int* h, const int* w, uint8_t* const* out, unsigned* hist,
+                                hipStream_t s);
+size_t moments_labeled_workspace_bytes(int C, long npix, int K);
+hipError_t launch_moments_labeled(const float* feat, int C, long npix, const uint8_t* lab, int K, double* n, double* sum, double* sumsq,
+                                  void* workspace, size_t workspace_bytes, hipStream_t s, bool f32_products);
+size_t apply_labeled_workspace_bytes(int C, int K);
+hipError_t launch_apply_labeled(const float* feat, int C, long npix, const uint8_t* lab, int K, const double* M, const double* b,
+                                float* out, void* workspace, size_t workspace_bytes, hipStream_t s);
+hipError_t launch_mb_identity(double* M, double* b, int C, int K, unsigned mask, hipStream_t s);

@@ -55,6 +55,10 @@ def build_parser() -> argparse.ArgumentParser:
                    help="uint8 conversion of the result: 0 = truncation (torchvision 0.2.1, the reference's pin), 1 = +0.5")
     p.add_argument("--pipeline", type=int, default=3, help="pairs in flight (decode-ahead, async copies, writer pool); 0 = the reference's serial loop")
     p.add_argument("--io_threads", type=int, default=8, help="threads of the decode pool and of the writer pool (--pipeline > 0)")
+    # not in the reference: spatial control (wct_stylize_regions)
+    p.add_argument("--maskPath", type=str, default=None,
+                   help="folder of label maps: content X.* uses DIR/X.png (mode L or P, pixel value = index into --region_styles, 255 = unstyled)")
+    p.add_argument("--region_styles", type=str, default=None, help="comma-separated style images of the regions (with --maskPath)")
     return p
 
 
@@ -110,6 +114,89 @@ def load_rgb_u8(path: str, size: int = 0):
                 oh, ow = size, int(size * w / h)
             img = img.resize((ow, oh), Image.BILINEAR)
     return np.array(img, dtype=np.uint8)   # a writable, contiguous copy
+
+
+def resized_shape(H: int, W: int, size: int) -> Tuple[int, int]:
+    """(H, W) after transforms.Resize(size) (data_loader.py:52-56; the rule of load_rgb_u8 and wct_resize_shape)."""
+    if not size or (W <= H and W == size) or (H <= W and H == size):
+        return H, W
+    if W < H:
+        return int(size * H / W), size
+    return size, int(size * W / H)
+
+
+def region_jobs(content_dir: str, mask_dir: str, content_mark: str = ".") -> List[Tuple[str, str]]:
+    """--maskPath: every content X.* (listdir order, --picked_content_mark) with its label map DIR/X.png (X = text before the first
+    dot, as pair_name); a content without a map is an error that names the missing file."""
+    jobs = []
+    for c in os.listdir(content_dir):
+        if not (is_image_file(c) and content_mark in c):
+            continue
+        m = os.path.join(mask_dir, c.split(".")[0] + ".png")
+        if not os.path.isfile(m):
+            raise FileNotFoundError("label map %s for content %s not found" % (m, c))
+        jobs.append((c, m))
+    return jobs
+
+
+def load_mask(path: str, shape: Tuple[int, int]):
+    """A label map as uint8 H x W: a mode L or P PNG whose pixel values are region indices.  It must have the content's size after
+    --content_size (`shape`); masks are never resampled."""
+    import numpy as np
+    from PIL import Image
+    img = Image.open(path)
+    if img.mode not in ("L", "P"):
+        raise ValueError("label map %s has mode %s; expected L or P (pixel value = region index)" % (path, img.mode))
+    lab = np.array(img, dtype=np.uint8)
+    if tuple(lab.shape) != tuple(shape):
+        raise ValueError("label map %s is %dx%d (HxW) but the content is %dx%d after --content_size; masks are not resampled"
+                         % (path, lab.shape[0], lab.shape[1], shape[0], shape[1]))
+    return lab
+
+
+def region_out_name(args, content_file: str) -> str:
+    """<log_mark>_mode=<m>_alpha=<a>_<X>+regions.jpg (out_name with the style stem replaced by 'regions')."""
+    return out_name(args, content_file.split(".")[0] + "+regions.jpg")
+
+
+def run_regions(args, wct, content_dir, logprinter) -> float:
+    """--maskPath: one stylisation per content, region k against --region_styles[k] (wct_stylize_regions); the serial loop."""
+    import torch
+    from PIL import Image
+    jobs = region_jobs(content_dir, args.maskPath, args.picked_content_mark)
+    styles = [p for p in args.region_styles.split(",") if p]
+    s_dev = [_to_tensor(wct, torch.from_numpy(load_rgb_u8(p)).cuda(), args.style_size) for p in styles]
+    avg = 0.0
+    for i, (cfile, mpath) in enumerate(jobs):
+        logprinter("\n" + "*" * 30 + ' #%s: Transferring "%s" by regions (%s)' % (i, cfile, mpath))
+        c_u8 = torch.from_numpy(load_rgb_u8(os.path.join(content_dir, cfile))).pin_memory().cuda(non_blocking=True)
+        H, W = resized_shape(int(c_u8.shape[0]), int(c_u8.shape[1]), args.content_size)
+        lab = torch.from_numpy(load_mask(mpath, (H, W))).cuda()
+        t0 = time.time()
+        c_f32 = _to_tensor(wct, c_u8, args.content_size)
+        res = wct.stylize_regions(c_f32, s_dev, lab, args.alpha, args.num_run)
+        if wct.saturation_count(reset=True):
+            logprinter("WARNING: f16x3 range exceeded for this content -> recomputing it with exact-fp32 convolutions")
+            wct.set_conv_mode("fp32")
+            s32 = [_to_tensor(wct, torch.from_numpy(load_rgb_u8(p)).cuda(), args.style_size) for p in styles]
+            res = wct.stylize_regions(c_f32, s32, lab, args.alpha, args.num_run)
+            wct.sync()
+            wct.set_conv_mode("f16x3")
+        out = wct.to_u8(res, args.round_mode).cpu().numpy()
+        Image.fromarray(out).save(region_out_name(args, cfile))
+        dt = time.time() - t0
+        avg += dt
+        logprinter("Elapsed time is: %.4f seconds" % dt)
+    return avg
+
+
+def check_region_args(args) -> None:
+    if (args.maskPath is None) != (args.region_styles is None):
+        raise ValueError("--maskPath and --region_styles go together")
+    if args.region_styles is not None:
+        n = len([p for p in args.region_styles.split(",") if p])
+        if not 1 <= n <= 8:
+            raise ValueError("--region_styles: 1 to 8 style images, got %d" % n)
 
 
 class LogPrinter:     # WCT.py:78-82
@@ -315,6 +402,7 @@ def run_pipelined(args, wct, pairs, content_dir, style_dir, logprinter) -> float
 def main(argv: Optional[List[str]] = None) -> int:
     args = build_parser().parse_args(argv)
     checkpoint_args(args)
+    check_region_args(args)
     if args.synthesis:
         raise NotImplementedError("--synthesis is broken in the reference (data_loader.py:74) and not part of this path")
     os.makedirs(args.outf, exist_ok=True)
@@ -322,6 +410,17 @@ def main(argv: Optional[List[str]] = None) -> int:
     logprinter(sorted(vars(args).items()))
     content_dir = args.UHD_contentPath if args.UHD else args.contentPath
     style_dir = args.UHD_stylePath if args.UHD else args.stylePath
+    if args.maskPath is not None:
+        jobs = region_jobs(content_dir, args.maskPath, args.picked_content_mark)
+        from .wct import WCT
+        wct = WCT(args)
+        logprinter("Number of contents with label maps: %s" % len(jobs))
+        if args.pipeline > 0:
+            logprinter("--pipeline is ignored with --maskPath: region runs use the serial loop")
+        avg = run_regions(args, wct, content_dir, logprinter)
+        if jobs:
+            logprinter("Processed %d images. Average processing time per image is: %.4f seconds" % (len(jobs), avg / len(jobs)))
+        return 0
     pairs = list_pairs(content_dir, style_dir, args.picked_content_mark, args.picked_style_mark)
 
     from .wct import WCT      # raises ImportError if libwct_hip.so is missing: no CPU fallback

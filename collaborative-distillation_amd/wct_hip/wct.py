@@ -658,6 +658,75 @@ class WCT:
                                         out.data_ptr(), byref(ho), byref(wo)))
         return out.view(-1)[: 3 * ho.value * wo.value].view(1, 3, ho.value, wo.value)
 
+    # ------------------------------------------------------------------ spatial control (regions)
+    def _labels(self, labels: torch.Tensor, h: int, w: int) -> torch.Tensor:
+        if labels.dtype != torch.uint8 or tuple(labels.shape) != (h, w):
+            raise ValueError("labels must be a uint8 tensor of shape (%d, %d), got %s %s" % (h, w, labels.dtype, tuple(labels.shape)))
+        return labels.to(self.stats_device).contiguous()
+
+    @torch.no_grad()
+    def moments_labeled(self, feat_nhwc: torch.Tensor, labels: torch.Tensor, K: int):
+        """Raw fp64 sums per label k < K of an NHWC feature [1,h,w,C] with an (h, w) uint8 label map: (n[K], sum[K,C], sumsq[K,C,C])."""
+        f = self._nhwc(feat_nhwc)
+        h, w, C = (int(v) for v in f.shape)
+        lab = self._labels(labels, h, w)
+        n = torch.empty(K, device=f.device, dtype=torch.float64)
+        s = torch.empty(K, C, device=f.device, dtype=torch.float64)
+        ss = torch.empty(K, C, C, device=f.device, dtype=torch.float64)
+        self._stream()
+        self._chk(self._lib.wct_moments_labeled(self._ctx, f.data_ptr(), C, h, w, lab.data_ptr(), int(K), n.data_ptr(), s.data_ptr(), ss.data_ptr()))
+        return n, s, ss
+
+    @torch.no_grad()
+    def apply_labeled(self, feat: torch.Tensor, labels: torch.Tensor, M: torch.Tensor, b: torch.Tensor, layout: str = "nhwc") -> torch.Tensor:
+        """out_p = M[lab(p)] feat_p + b[lab(p)] with M [K,C,C], b [K,C]; labels >= K (255) copied through.  feat is [1,h,w,C] (nhwc) or
+        [1,C,h,w] (nchw); the result has the same shape."""
+        f = feat[0] if feat.dim() == 4 else feat
+        if f.dim() != 3:
+            raise ValueError("expected a feature map [1,h,w,C] / [1,C,h,w], got %s" % (tuple(feat.shape),))
+        f = self._dev_f32(f)
+        nchw = layout == "nchw"
+        if nchw:
+            C, h, w = (int(v) for v in f.shape)
+        else:
+            h, w, C = (int(v) for v in f.shape)
+        K = int(b.shape[0]) if b.dim() == 2 else int(b.numel()) // C
+        lab = self._labels(labels, h, w)
+        M, b = self._dev_f64(M, K * C * C, "M"), self._dev_f64(b, K * C, "b")
+        out = torch.empty((1,) + tuple(f.shape), device=f.device, dtype=torch.float32)
+        self._stream()
+        self._chk(self._lib.wct_apply_labeled(self._ctx, f.data_ptr(), C, h, w, _lib.LAYOUT_NCHW if nchw else _lib.LAYOUT_NHWC,
+                                              lab.data_ptr(), K, M.data_ptr(), b.data_ptr(), out.data_ptr()))
+        return out
+
+    @torch.no_grad()
+    def stylize_regions(self, contentImg: torch.Tensor, styles, labels: torch.Tensor, alpha=None, num_run: int = 1,
+                        out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The cascade with spatial control: `labels` (uint8 H x W, CUDA) gives each content pixel a style index k < len(styles) or 255
+        (unstyled); `alpha` is one float or one per style.  Region k is whitened / coloured with its own statistics against style k."""
+        c = self._img(contentImg)
+        H, W = int(c.shape[1]), int(c.shape[2])
+        ss = [self._img(s) for s in styles]
+        K = len(ss)
+        if alpha is None:
+            alpha = self.alpha
+        al = [float(alpha)] * K if isinstance(alpha, (int, float)) else [float(a) for a in alpha]
+        if len(al) != K:
+            raise ValueError("alpha: expected 1 or %d values, got %d" % (K, len(al)))
+        if not labels.is_cuda:
+            raise ValueError("labels must be a CUDA uint8 tensor")
+        lab = self._labels(labels, H, W)
+        out = self._out_image(out, H, W)
+        ptrs = (c_void_p * max(K, 1))(*[s.data_ptr() for s in ss])
+        hs = (c_int * max(K, 1))(*[int(s.shape[1]) for s in ss])
+        ws = (c_int * max(K, 1))(*[int(s.shape[2]) for s in ss])
+        av = (ctypes.c_float * max(K, 1))(*al)
+        ho, wo = c_int(), c_int()
+        self._stream()
+        self._chk(self._lib.wct_stylize_regions(self._ctx, c.data_ptr(), H, W, lab.data_ptr(), K, ptrs, hs, ws, av, int(num_run),
+                                                out.data_ptr(), byref(ho), byref(wo)))
+        return out.view(-1)[: 3 * ho.value * wo.value].view(1, 3, ho.value, wo.value)
+
     def set_conv_mode(self, mode: str):
         """'f16x3' (default: split-f16 MFMA, fp32-class accuracy) or 'fp32' (exact fp32 MFMA)."""
         self._chk(self._lib.wct_set_conv_mode(self._ctx, {"fp32": 0, "f16x3": 1}[mode]))

@@ -300,6 +300,31 @@ int wct_style_solve(wct_ctx* ctx, int level, double n_s, const double* sum_s, co
 int wct_stylize(wct_ctx* ctx, const float* content, int H, int W, const float* style, int Hs, int Ws, float alpha,
                 int num_run, float* out, int* Ho, int* Wo);
 
+/* Spatial control: a uint8 label map gives every content pixel a region 0 .. K-1 with its own style, or 255 (unstyled); 1 <= K <= 8.
+ * Per region and level the transform is the reference's whiten_and_color (util_wct.py:62-131) on THAT REGION's feature columns, against
+ * the whole style image's statistics (WCT.py:121-125: the same style at every level), blended with alpha[k] (:219); a region with fewer
+ * than 2 feature pixels at a level, and label 255, keep cF there.  Level L reads the label at the centre of its pooling window in image
+ * coordinates: lab_L[i][j] = labels[i s + s/2][j s + s/2], s = 2^(L-1).
+ *   wct_moments_labeled  extends wct_moments: per label k < K, n[k] pixels, sum[k*C + c], sumsq[k*C*C + a*C + b] (device f64) of an NHWC
+ *                        map, lab h x w (device).  Same arithmetic classes as wct_moments (fp32 products in blocks of <= 64 pixels with
+ *                        fp64 block totals for maps of >= 65 536 pixels, fp64 products below; "mom32" applies), fixed-order reduction:
+ *                        bitwise reproducible.  Pixels with labels >= K are ignored.
+ *   wct_apply_labeled    extends wct_apply: out_p = M[lab(p)] feat_p + b[lab(p)], M [K*C*C], b [K*C] device f64 (used in fp32, fp32
+ *                        accumulation); pixels with labels >= K (255) are copied through.  layout as wct_apply.
+ *   wct_stylize_regions  extends wct_stylize (WCT.py:120-125): content 3 x H x W, labels H x W (device), K styles (device pointers in a
+ *                        HOST array, each 3 x Hs[k] x Ws[k]), alpha[K] (HOST).  Per level: encoder -> wct_moments_labeled -> one content
+ *                        solve per region against style k -> wct_apply_labeled -> decoder (unfolded first conv); the K style sides run on
+ *                        the side stream.  The call reads the label histograms back ONCE at its start (one stream synchronisation: the
+ *                        solvers take each region's pixel count on the host), so it cannot be captured into a HIP graph.  K outside
+ *                        [1, 8] or a label value >= K other than 255 anywhere in the map return WCT_ERR_INVALID before anything is
+ *                        written to out; wct_last_error names the smallest offending value.  out must hold 3*H*W floats. */
+int wct_moments_labeled(wct_ctx* ctx, const float* feat, int C, int h, int w, const uint8_t* lab, int K, double* n, double* sum,
+                        double* sumsq);
+int wct_apply_labeled(wct_ctx* ctx, const float* feat, int C, int h, int w, int layout, const uint8_t* lab, int K, const double* M,
+                      const double* b, float* out);
+int wct_stylize_regions(wct_ctx* ctx, const float* content, int H, int W, const uint8_t* labels, int K, const float* const* styles,
+                        const int* Hs, const int* Ws, const float* alpha, int num_run, float* out, int* Ho, int* Wo);
+
 /* Style statistics cache.  wct_style_prepare leaves, per level, the style mean and cov^(1/2) inside the
  * context; they depend only on the style image, so
  *   wct_stylize_prepared  runs the content cascade against them (no style-side work): content x style batches pay
