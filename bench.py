@@ -1,8 +1,13 @@
 #!/usr/bin/env python3
 """Benchmark of the MI355X-native WCT stylisation path.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]          (N > 1: under torch.distributed.run, or plainly -- it then
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full]   (N > 1: under torch.distributed.run, or plainly -- it then
                                                                   launches itself that way, one process per GPU)
+
+A plain run sets up, runs W warm-up and K timed steps, writes --dump-outputs if asked, and prints the line: metric, value, unit,
+ms_per_step, dtype, config, and parity_ok / parity from the f16x3 saturation count of those steps (no further check).  Everything
+else below -- telemetry, sustained and latency figures, roofline and kernels, passes, cpu_baseline and the parity gate against the
+reference -- runs only with --full.  (N > 1: the first-contact check that picks the timed path is set-up and runs either way.)
 
 A "step" is one end-to-end 5-level WCT stylisation (levels 5..1; style-side encodes, moments and matrix functions INCLUDED) of
 synthetic images already resident in HBM (fp32, planar 3xHxW).  The frames are the SURVEY 8(d) ones: uniform noise from
@@ -23,7 +28,7 @@ Sharding (wct_hip/sharded.py): per level one RCCL all-reduce of the fp64 content
 statistics (or of the colouring map (M, b)), and -- for strips narrower than 2560 columns -- a neighbour exchange of the
 decoded edge columns instead of recomputed cumulative halos.  value = content megapixels / second over all ranks.
 
-The JSON line also carries
+With --full the JSON line also carries
   roofline      dominant kernel family: algorithmic FLOP per launch / HIP-event duration vs the f16x3 MFMA roofline
   passes        relu4_1 encode pass (364 B/px, 30 816 FLOP/px); the cascade against cached style statistics and
                 with three frames in flight (cfg5_per_gpu); configs[3]'s frame untiled on one GPU; configs[2] (cfg3_original);
@@ -83,7 +88,7 @@ def source_id():
 
 def live_pmc(config, timeout=90):
     """The two PMC passes of MI355X_MICROARCH.md's HBM recipe, taken NOW: counters cannot be read from inside this process, so a
-    bounded copy of this very command (`--steps-only`, 1 warm-up + 2 steps, kernels one at a time) runs twice as a child under
+    bounded copy of this very command (`--full --steps-only`, 1 warm-up + 2 steps, kernels one at a time) runs twice as a child under
     `rocprofv3 --kernel-trace --pmc FETCH_SIZE` / `... WRITE_SIZE` (separate passes, nothing else traced) while this process idles,
     and tools/pmc_summary.py turns the two counter tables into bytes per launch.  -> path of the summary json, or None (no
     rocprofv3, a failed or overlong pass: the caller then falls back to the committed profile and says so)."""
@@ -103,7 +108,7 @@ def live_pmc(config, timeout=90):
             out = os.path.join(tmp, counter)
             cmd = [rocprof, "--kernel-trace", "--pmc", counter, "--output-format", "csv", "-d", out, "-o", "pmc", "--",
                    sys.executable, os.path.abspath(__file__), "--config", config, "--steps", "2", "--warmup", "1",
-                   "--no-cpu-baseline", "--steps-only"]
+                   "--full", "--no-cpu-baseline", "--steps-only"]
             r = subprocess.run(cmd, cwd="/tmp", env=env, timeout=timeout, stdout=subprocess.DEVNULL, stderr=subprocess.PIPE)
             found = [os.path.join(d, f) for d, _, fs in os.walk(out) for f in fs if f.endswith("counter_collection.csv")]
             if r.returncode != 0 or not found:
@@ -141,7 +146,7 @@ def pmc_traffic(family, live=None):
     ks = doc["kernels"]
     src = {"file": "profiles/hbm_traffic_latest.json", "profiled_source_id": doc.get("source_id"), "source_id": source_id()}
     if live:
-        src["file"] = "live: rocprofv3 --kernel-trace --pmc FETCH_SIZE | WRITE_SIZE around `bench.py --steps-only --steps 2` children of this run"
+        src["file"] = "live: rocprofv3 --kernel-trace --pmc FETCH_SIZE | WRITE_SIZE around `bench.py --full --steps-only --steps 2` children of this run"
     src["stale"] = src["profiled_source_id"] != src["source_id"]
     # the fused full-resolution ends and the level-1 kernels: one device kernel per family (prefix match on the demangled name)
     prefix = {"enc_head_fused": ("void enc_head_roles_kernel<", "void enc_head_kernel<"), "dec_tail_fused": ("void dec_tail_up_kernel<", "void dec_tail_kernel<"),
@@ -436,11 +441,14 @@ def main():
                          "cfg4: ONE 10240x4096 content in N column strips (strong scaling); cfg3: --mode original at 1920x1080 (N = 1)")
     ap.add_argument("--halo-mode", choices=["auto", "recompute", "exchange"], default="auto")
     ap.add_argument("--debug-set", action="append", default=[], metavar="KEY=VALUE", help="wct_debug_set switches for A/B runs")
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU oracle run (the parity gate then has no oracle arm)")
-    ap.add_argument("--no-live-pmc", action="store_true", help="roofline.traffic from the committed profile instead of two rocprofv3 "
-                                                               "--pmc child runs of this command (~1 min)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure and check everything beyond the headline: telemetry, sustained and latency "
+                         "figures, roofline and kernels, the extra passes, the CPU baseline and the parity gate against the reference")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle run (the parity gate then has no oracle arm)")
+    ap.add_argument("--no-live-pmc", action="store_true", help="with --full: roofline.traffic from the committed profile instead of two "
+                                                               "rocprofv3 --pmc child runs of this command (~1 min)")
     ap.add_argument("--steps-only", action="store_true",
-                    help="skip the extra passes and the parity leg: every launch then belongs to a stylise step, so a rocprofv3 "
+                    help="with --full: skip the extra passes and the parity leg: every launch then belongs to a stylise step, so a rocprofv3 "
                          "--stats summary of the run averages the same launch mix as `roofline`")
     ap.add_argument("--dump-outputs", metavar="DIR",
                     help="write what the last timed step returned to DIR/output.npy (N > 1: DIR/output_rank<r>.npy, each rank its strip), "
@@ -692,7 +700,8 @@ def main():
     step, mp, desc, content = make_step(args.config, wct)
     collectives_timed = collectives_used[0]
     wct.saturation_count(reset=True)
-    tele = Telemetry(dev) if rank == 0 else None
+    full = args.full
+    tele = Telemetry(dev) if rank == 0 and full else None
     for _ in range(args.warmup):
         step()
     if tele:
@@ -738,16 +747,16 @@ def main():
                                                    "latency_ms_at_2200MHz": round(float(a + b), 3)}
         return res
 
-    sustained = sustained_block() if not args.steps_only else None
+    sustained = sustained_block() if full and not args.steps_only else None
     telemetry = tele.stop() if tele else None
     if last is not None:
         dump_outputs(args.dump_outputs, {"output" if world == 1 else "output_rank%d" % rank: last}, DUMP_BUDGET_BYTES // world)
     del last
     saturated = wct.saturation_count()      # threads that clamped an activation to the f16x3 range during the timed steps
-    lat_med, lat_min, lat_max = latency_median(step, max(10, min(args.steps, 20)))
-
-    # ---- roofline leg (rank 0 records; every rank runs the steps: they contain collectives)
-    profile, roof, _ = kernel_profile(wct, step, record=(rank == 0))
+    if full:
+        lat_med, lat_min, lat_max = latency_median(step, max(10, min(args.steps, 20)))
+        # ---- roofline leg (rank 0 records; every rank runs the steps: they contain collectives)
+        profile, roof, _ = kernel_profile(wct, step, record=(rank == 0))
 
     def sharded_vs_untiled(runner, strip_in, cfg, fw, frame=None):
         """N > 1 parity, part (b): this rank's owned strip of the sharded frame against the UNTILED frame computed on this same GPU by the
@@ -764,7 +773,7 @@ def main():
         return float(t.item())
 
     sharded_parity = None
-    if world > 1 and not args.steps_only:
+    if world > 1 and full and not args.steps_only:
         fw_ = {"cfg2": W * world, "cfg4": W4}[args.config]
         # bound: the sharded tests' -- 5e-4; 1e-3 on the 4096-row config-4 frame (tests/test_sharded_gpu.py: sharded and untiled (M, b) differ
         # by ~1e-8 in the moments, which the five whitenings of a 42 MP noise frame amplify further than those of an 8 MP one)
@@ -773,7 +782,7 @@ def main():
     del step
 
     # ---- extra passes (never `value`)
-    extra = not args.steps_only
+    extra = full and not args.steps_only
     passes = {}
     if extra and world > 1 and args.config == "cfg2":
         # BASELINE configs[3] beside the weak-scaling number: ONE 10240x4096 frame in N strips (strong scaling)
@@ -1048,34 +1057,40 @@ def main():
         parity = {"f16x3_saturated_threads": int(saturated)}
 
     if rank == 0:
-        # HBM bytes per launch of the dominant kernels: PMC passes taken now (N = 1 default run), else the committed profile (a
-        # number, or null).  LAST, with every timed pass done: the GPU idles while the children run, and a pass timed right
-        # after them ran on cold clocks (relu4_1_encode 0.89 -> 1.05 ms when this sat in front of the passes).
-        live_ok = world == 1 and not args.steps_only and not args.no_live_pmc
-        live = live_pmc(args.config) if live_ok else None
-        pm = pmc_traffic(roof["kernel"], live) or pmc_traffic(roof["kernel"])
-        roof["traffic"], roof["traffic_source"] = (pm[0], pm[1]) if pm else (None, None)
-        # what ran the timed steps (inside `roofline` so that a record keeping only this object still says what the device did)
-        roof["device"] = {"sclk_MHz_avg": (telemetry or {}).get("sclk_MHz_avg"), "power_W_avg": (telemetry or {}).get("power_W_avg"),
-                          "ms_per_step": round(dt / args.steps * 1e3, 3),
-                          "ms_per_step_sustained": (sustained or {}).get("ms_per_step_sustained"),
-                          "latency_ms_scaled_to_2200MHz": (sustained or {}).get("latency_ms_scaled_to_2200MHz"),
-                          "latency_ms_at_2200MHz_two_box_model": (sustained or {}).get("latency_ms_at_2200MHz_two_box_model")}
-        r3 = passes.get("cfg3_original", {}).get("roofline") if args.config != "cfg3" else None
-        if r3 and live:      # (not attempted when the first collection failed: bounded run time)
-            live3 = live_pmc("cfg3")
-            pm3 = pmc_traffic(r3["kernel"], live3) if live3 else None
-            r3["traffic"], r3["traffic_source"] = (pm3[0], pm3[1]) if pm3 else (None, None)
+        if full:
+            # HBM bytes per launch of the dominant kernels: PMC passes taken now (N = 1 full run), else the committed profile (a
+            # number, or null).  LAST, with every timed pass done: the GPU idles while the children run, and a pass timed right
+            # after them ran on cold clocks (relu4_1_encode 0.89 -> 1.05 ms when this sat in front of the passes).
+            live_ok = world == 1 and not args.steps_only and not args.no_live_pmc
+            live = live_pmc(args.config) if live_ok else None
+            pm = pmc_traffic(roof["kernel"], live) or pmc_traffic(roof["kernel"])
+            roof["traffic"], roof["traffic_source"] = (pm[0], pm[1]) if pm else (None, None)
+            # what ran the timed steps (inside `roofline` so that a record keeping only this object still says what the device did)
+            roof["device"] = {"sclk_MHz_avg": (telemetry or {}).get("sclk_MHz_avg"), "power_W_avg": (telemetry or {}).get("power_W_avg"),
+                              "ms_per_step": round(dt / args.steps * 1e3, 3),
+                              "ms_per_step_sustained": (sustained or {}).get("ms_per_step_sustained"),
+                              "latency_ms_scaled_to_2200MHz": (sustained or {}).get("latency_ms_scaled_to_2200MHz"),
+                              "latency_ms_at_2200MHz_two_box_model": (sustained or {}).get("latency_ms_at_2200MHz_two_box_model")}
+            r3 = passes.get("cfg3_original", {}).get("roofline") if args.config != "cfg3" else None
+            if r3 and live:      # (not attempted when the first collection failed: bounded run time)
+                live3 = live_pmc("cfg3")
+                pm3 = pmc_traffic(r3["kernel"], live3) if live3 else None
+                r3["traffic"], r3["traffic_source"] = (pm3[0], pm3[1]) if pm3 else (None, None)
         cfg = args.config
         mode = "original (generated weights)" if cfg == "cfg3" else "16x"
         line = {
             "metric": "content megapixels/sec, end-to-end 5-level WCT (%s)" % {"cfg2": "16x VGG, 4K content, 2K style", "cfg4": "16x VGG, 10240x4096 content, 2K style",
                                                                               "cfg3": "un-pruned VGG-19, generated weights, 1920x1080"}[cfg],
             "value": (round(value, 2) if parity_ok is not False else None), "unit": "MP/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(dt / args.steps * 1e3, 3), "latency_ms_median": lat_med, "latency_ms_min_max": [lat_min, lat_max],
-            "latency_note": "SURVEY 8(d): each frame synchronised on its own, median of >= 10 (a lone call cannot hide its launch "
-                            "latency or its style lane's tail behind the next frame); `value` / ms_per_step = K back-to-back steps, one sync",
-            "gpu_telemetry": telemetry, "sustained": sustained, "higher_is_better": True, "scaling": "strong" if cfg == "cfg4" else "weak",
+            "ms_per_step": round(dt / args.steps * 1e3, 3)}
+        if full:
+            line.update({
+                "latency_ms_median": lat_med, "latency_ms_min_max": [lat_min, lat_max],
+                "latency_note": "SURVEY 8(d): each frame synchronised on its own, median of >= 10 (a lone call cannot hide its launch "
+                                "latency or its style lane's tail behind the next frame); `value` / ms_per_step = K back-to-back steps, one sync",
+                "gpu_telemetry": telemetry, "sustained": sustained})
+        line.update({
+            "higher_is_better": True, "scaling": "strong" if cfg == "cfg4" else "weak",
             "vs_baseline": None, "dtype": "f32 (f16x3 split-MFMA products, fp32 accumulate)", "data": "synthetic",
             "parity_ok": parity_ok, "parity": parity,
             "config": {"workload": "PytorchWCT/WCT.py --mode %s, 5-level WCT, %s, alpha=1, style-side work included, images resident in HBM; %s"
@@ -1083,9 +1098,9 @@ def main():
                                                    "cfg3": "BASELINE configs[2]", "cfg4": "BASELINE configs[3] (strong scaling)"}[cfg]),
                        "name": ("cfg2" if world == 1 else "cfg2x%d" % world) if cfg == "cfg2" else cfg,
                        "content_total": "%dx%d" % {"cfg2": (W * world, H), "cfg3": (W3, H3), "cfg4": (W4, H4)}[cfg], "parallelism": "content column strips x%d" % world,
-                       "dist_backend": (backend if world > 1 else None), "collectives": collectives_timed},
-            "roofline": roof, "passes": passes or None, "cpu_baseline": cpu, "kernels": profile,
-        }
+                       "dist_backend": (backend if world > 1 else None), "collectives": collectives_timed}})
+        if full:
+            line.update({"roofline": roof, "passes": passes or None, "cpu_baseline": cpu, "kernels": profile})
         if parity_ok is False:
             line["unverified_value"] = round(value, 2)
         os.write(line_fd, (json.dumps(line) + "\n").encode())

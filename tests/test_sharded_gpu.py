@@ -644,7 +644,7 @@ def test_bench_two_ranks_on_one_gpu(extra, name):
     sharing the one GPU over gloo: the JSON contract of the multi-rank line, both workloads."""
     env = dict(os.environ, WCT_DIST_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1"] + extra
+           "--master-port", str(_free_port()), os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full"] + extra
     r = subprocess.run(cmd, env=env, cwd=REPO, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -931,7 +931,7 @@ def test_style_strip_margins_reproduce_the_untiled_features():
 @needs_two_devices
 def test_bench_two_devices_rccl_self_launched():
     """`python bench.py --gpus 2` as the driver types it, on two real devices: self-launched under torch.distributed.run, RCCL."""
-    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1"],
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full"],
                        env={k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "WCT_DIST_BACKEND")},
                        cwd=REPO, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -947,7 +947,7 @@ def test_bench_launches_itself_for_n_ranks():
     missing #1: it used to die on a usage message): the script re-executes itself under torch.distributed.run --nproc-per-node 2 on
     127.0.0.1 and rank 0 prints the ONE line.  On this box's single device the ranks share it over gloo, and the line says so."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "WCT_DIST_BACKEND")}
-    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--steps-only"],
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--steps-only"],
                        env=env, cwd=REPO, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -960,10 +960,10 @@ def test_bench_launches_itself_for_n_ranks():
 
 @pytest.mark.parametrize("cfg,name,total", [("cfg3", "cfg3", "1920x1080"), ("cfg2", "cfg2", "3840x2160")])
 def test_bench_single_gpu_line_contract(cfg, name, total):
-    """bench.py on one GPU, short (--steps-only leaves out the CPU oracle, the parity leg and the extra passes): exactly ONE line on
+    """bench.py --full on one GPU, short (--steps-only leaves out the CPU oracle, the parity leg and the extra passes): exactly ONE line on
     stdout -- whatever RCCL or the runtime print goes to stderr -- with the fields the driver reads, for the default configuration
     and for --config cfg3 (--mode original, generated weights)."""
-    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--steps", "2", "--warmup", "1", "--steps-only", "--no-cpu-baseline", "--config", cfg]
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--steps", "2", "--warmup", "1", "--full", "--steps-only", "--no-cpu-baseline", "--config", cfg]
     r = subprocess.run(cmd, cwd=REPO, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -982,6 +982,26 @@ def test_bench_single_gpu_line_contract(cfg, name, total):
     assert line["roofline"]["kernel"] == top["kernel"]
     assert roof["bound"] in ("mfma", "hbm") and 0 < roof["frac"] < 1 and roof["achieved"] > 0 and roof["peak"] > 0 and "traffic" in roof
     assert abs(line["value"] - float(total.split("x")[0]) * float(total.split("x")[1]) / 1e6 / line["ms_per_step"] * 1e3) < 0.02 * line["value"]
+
+
+def test_bench_plain_run_is_lean(tmp_path):
+    """A plain bench.py run (no --full) sets up, warms up, times the steps, dumps the last one and prints the headline line: the
+    fields the driver reads, none of the --full measurements, and --dump-outputs written from the last timed step."""
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path)]
+    r = subprocess.run(cmd, cwd=REPO, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1 and lines[0].startswith("{"), r.stdout[-2000:]
+    line = json.loads(lines[0])
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "steps", "warmup", "config"):
+        assert key in line, key
+    for key in ("roofline", "kernels", "passes", "cpu_baseline", "latency_ms_median", "gpu_telemetry", "sustained"):
+        assert key not in line, key
+    assert line["n_gpus"] == 1 and line["steps"] == 2 and line["unit"] == "MP/s" and line["higher_is_better"] is True
+    assert line["value"] > 0 and line["parity_ok"] is None and line["config"]["content_total"] == "3840x2160"
+    assert abs(line["value"] - 3840 * 2160 / 1e6 / line["ms_per_step"] * 1e3) < 0.02 * line["value"]
+    out = np.load(tmp_path / "output.npy")      # 3 x 2160 x 3840 floats exceed the dump budget: a seeded sample of them
+    assert out.dtype == np.float32 and 0 < out.size <= (64 << 20) // 4 and np.isfinite(out).all()
 
 
 def test_strip_halos_exact_with_level_margins(tmp_path):

@@ -1,5 +1,5 @@
 #!/bin/bash
-# Same-box, interleaved A/B of one context debug key (wct_debug_set) on the timed loop: ms_per_step of `bench.py --steps-only` and the
+# Same-box, interleaved A/B of one context debug key (wct_debug_set) on the timed loop: ms_per_step of `bench.py --full --steps-only` and the
 # kernel families that moved.   usage (GPU box): tools/experiments/ab_debug_key.sh KEY "V1 V2 ..." [cfg2|cfg3] [rounds]
 #   -> gpurun_out/ab_<KEY>_<cfg>.txt
 KEY=$1; VALS=${2:-"0 1"}; CFG=${3:-cfg2}; ROUNDS=${4:-3}
@@ -7,7 +7,7 @@ OUT=gpurun_out/ab_${KEY}_${CFG}.txt
 mkdir -p gpurun_out; : > $OUT
 for r in $(seq 1 $ROUNDS); do
   for v in $VALS; do
-    python bench.py --config $CFG --steps 20 --warmup 3 --steps-only --no-cpu-baseline --debug-set $KEY=$v 2>/dev/null > /tmp/ab_line.json
+    python bench.py --config $CFG --steps 20 --warmup 3 --full --steps-only --no-cpu-baseline --debug-set $KEY=$v 2>/dev/null > /tmp/ab_line.json
     python - "$KEY" "$v" "$r" "$CFG" <<'PY' | tee -a $OUT
 import json, sys
 d = json.load(open("/tmp/ab_line.json"))

@@ -3,7 +3,7 @@
 #   FILTERS="enc_head dec_tail" tools/experiments/ab_envs.sh "" "VAR=1" "VAR=2 OTHER=3"
 for i in 1 2; do
   for e in "$@"; do
-    env WCT_DEBUG=1 $e python bench.py --steps 20 --warmup 3 --no-cpu-baseline --steps-only 2>/dev/null | TAG="${e:-default}" python -c "
+    env WCT_DEBUG=1 $e python bench.py --steps 20 --warmup 3 --full --no-cpu-baseline --steps-only 2>/dev/null | TAG="${e:-default}" python -c "
 import json,sys,os
 d=json.loads(sys.stdin.read())
 ks={k['kernel']:k['ms_per_step'] for k in d['kernels']}

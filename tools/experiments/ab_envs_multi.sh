@@ -3,7 +3,7 @@
 VAR=$1; VALS=$2; shift; shift
 for i in 1 2; do
   for v in $VALS; do
-    env WCT_DEBUG=1 $VAR=$v python bench.py --steps 20 --warmup 3 --no-cpu-baseline --steps-only 2>/dev/null | TAG="$VAR=$v" python -c "
+    env WCT_DEBUG=1 $VAR=$v python bench.py --steps 20 --warmup 3 --full --no-cpu-baseline --steps-only 2>/dev/null | TAG="$VAR=$v" python -c "
 import json,sys,os
 d=json.loads(sys.stdin.read())
 ks={k['kernel']:k['ms_per_step'] for k in d['kernels']}

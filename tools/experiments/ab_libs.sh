@@ -4,7 +4,7 @@
 LIBS=$1; shift
 for i in 1 2; do
   for lib in "" $LIBS; do
-    WCT_LIB_PATH=$lib python bench.py --steps 20 --warmup 3 --no-cpu-baseline --steps-only 2>/dev/null | LIBTAG=${lib:-current} python -c "
+    WCT_LIB_PATH=$lib python bench.py --steps 20 --warmup 3 --full --no-cpu-baseline --steps-only 2>/dev/null | LIBTAG=${lib:-current} python -c "
 import json,sys,os
 d=json.loads(sys.stdin.read())
 ks={k['kernel']:k['ms_per_step'] for k in d['kernels']}

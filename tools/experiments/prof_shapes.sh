@@ -1,4 +1,4 @@
-WCT_PROF_SHAPES=1 python bench.py --steps 6 --warmup 2 --no-cpu-baseline --steps-only 2>/dev/null | python -c "
+WCT_PROF_SHAPES=1 python bench.py --steps 6 --warmup 2 --full --no-cpu-baseline --steps-only 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 print('ms_per_step', d['ms_per_step'])

@@ -13,7 +13,7 @@ CFG=${2:-cfg2}
 OUT=$PWD/gpurun_out/prof_$TAG
 mkdir -p $OUT profiles
 export TMPDIR=/tmp
-CMD="python $PWD/bench.py --config $CFG --steps 4 --warmup 1 --no-cpu-baseline --steps-only"
+CMD="python $PWD/bench.py --config $CFG --steps 4 --warmup 1 --full --no-cpu-baseline --steps-only"
 ROOT=$PWD
 cd /tmp
 WCT_DEBUG=1 WCT_OVERLAP=0 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o stats -- $CMD > $OUT/stats_bench.log 2> $OUT/stats_bench.err || echo "stats pass failed"

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Regenerate the measured-figures blocks of README.md and DESIGN.md from ONE bench.py line (VERDICT r3 task 8: the documents used to quote
+"""Regenerate the measured-figures blocks of README.md and DESIGN.md from ONE `bench.py --full` line (VERDICT r3 task 8: the documents used to quote
 figures of builds that no longer existed).  The block between `<!-- BENCH:BEGIN -->` and `<!-- BENCH:END -->` in each file is replaced;
 everything else is prose and stays hand-written.   usage: python tools/update_docs.py profiles/r04x_bench_line.json"""
 import json, os, re, sys
@@ -14,7 +14,7 @@ roof = d.get("roofline", {})
 cpu = d.get("cpu_baseline") or {}
 cli = p.get("cli_pairs_per_s", {})
 g = lambda x, f="%.3g": (f % x) if isinstance(x, (int, float)) else "n/a"
-lines = ["_All figures in this block come from one `bench.py` line, `%s` (one MI355X; regenerate with `python tools/update_docs.py <line>`)._" % os.path.relpath(src, REPO), ""]
+lines = ["_All figures in this block come from one `bench.py --full` line, `%s` (one MI355X; regenerate with `python tools/update_docs.py <line>`)._" % os.path.relpath(src, REPO), ""]
 lines.append("* **Headline** (BASELINE configs[1]: `--mode 16x`, 3840×2160 content + 2048×2048 style, style side included): **%s ms per frame = %s MP/s**." % (g(d.get("ms_per_step"), "%.3f"), g(d.get("value"), "%.1f")))
 tel = d.get("gpu_telemetry") or {}
 lines.append("* Latency (SURVEY 8d: each frame synchronised on its own, median of >= 10): **%s ms** (min %s, max %s); GPU during the timed steps: %s W average (max %s), sclk %s MHz average (min %s)." % (
