@@ -145,6 +145,11 @@ struct wct_ctx {
   // the transformed feature map, the kernels' workspaces; pinned [6][256] label histograms read back once per call
   DevBuf eigR[8][6], eigCR[8], regLab, regHist, regSums, regMb, regFeat, wsRegMom, wsRegApply;
   unsigned* reg_hist_host = nullptr;
+  // style interpolation / weights (wct_stylize_interp, wct_style_blend, wct_stylize_blend): the pooled level weight maps, (V1, V2) per
+  // (level, k) + the weight check's counts, the pooling workspace, the mixed apply's workspace; pinned copy of blendStat read back once
+  // per wct_stylize_blend call (the regions' moments / maps / feature buffers are reused)
+  DevBuf blendW, blendStat, wsBlendPool, wsBlendApply;
+  void* blend_host = nullptr;
 };
 
 // RCCL, resolved at run time (wct_comm_load): the library keeps no link-time dependency on it
@@ -1057,6 +1062,8 @@ void wct_destroy(wct_ctx* ctx) {
   }
   for (DevBuf* b : {&ctx->regLab, &ctx->regHist, &ctx->regSums, &ctx->regMb, &ctx->regFeat, &ctx->wsRegMom, &ctx->wsRegApply}) release(*b);
   if (ctx->reg_hist_host) (void)hipHostFree(ctx->reg_hist_host);
+  for (DevBuf* b : {&ctx->blendW, &ctx->blendStat, &ctx->wsBlendPool, &ctx->wsBlendApply}) release(*b);
+  if (ctx->blend_host) (void)hipHostFree(ctx->blend_host);
 
   if (ctx->side.stream) (void)hipStreamDestroy(ctx->side.stream);
   if (ctx->sat_dev) (void)hipFree(ctx->sat_dev);
@@ -2200,6 +2207,295 @@ int wct_stylize_regions(wct_ctx* ctx, const float* content, int H, int W, const 
           for (int level = 5; level >= 1; --level) {
             float* dst = bufs[which];
             if (int rc = regions_level(ctx, level, cur, h, w, pl, K, alpha, dst)) return rc;
+            if (run == 0 && level > 1)
+              for (int k = 0; k < K; ++k)
+                if (int rc = style_side_slot(ctx, level - 1, k, styles[k], Hs[k], Ws[k])) return rc;
+            h = pl.h[level] << (level - 1); w = pl.w[level] << (level - 1);
+            cur = dst; which ^= 1;
+          }
+        if (cur != out) HIPCHK(ctx, hipMemcpyAsync(out, cur, (size_t)3 * h * w * sizeof(float), hipMemcpyDeviceToDevice, ctx->main.stream));
+        if (Ho) *Ho = h;
+        if (Wo) *Wo = w;
+        return WCT_OK;
+      })) return rc;
+  return range_readback(ctx);
+}
+
+}  // extern "C"
+
+// =====================================================================================================
+// Style interpolation (uniform weights) and per-pixel style weights (blend.hip).  The reference's whiten_and_color (util_wct.py:62-131)
+// is linear in the style statistics: sum_k lambda_k WCT(fc, fs_k) is the single-style transform against ONE blended style slot
+// (sum_k lambda_k cov_s,k^(1/2), sum_k lambda_k mu_s,k).  Weight maps generalise regions: per level, reliability-weighted content
+// moments per style and out_p = x_p + sum_k w_k(p) alpha_k (target_k(x_p) - x_p).
+namespace {
+int moments_weighted_impl(wct_ctx* ctx, Lane& ln, const float* feat, int C, int h, int w, const float* wts, int K, double* sum, double* sumsq) {
+  const long npix = (long)h * w;
+  if (int rc = ensure(ctx, ctx->wsRegMom, moments_weighted_workspace_bytes(C, npix, K))) return rc;
+  ProfScope ps(ctx, ln.stream, "moments_weighted", 2.0 * C * C * npix * K, 4.0 * C * npix + 4.0 * K * npix);
+  HIPCHK(ctx, launch_moments_weighted(feat, C, npix, wts, K, sum, sumsq, ctx->wsRegMom.p, ctx->wsRegMom.cap, ln.stream, mom32_on(ctx, npix)));
+  return WCT_OK;
+}
+
+int apply_mixed_impl(wct_ctx* ctx, const float* feat, int C, long npix, const float* wts, int K, const double* M, const double* b, float* out) {
+  if (int rc = ensure(ctx, ctx->wsBlendApply, apply_mixed_workspace_bytes(C, K))) return rc;
+  ProfScope ps(ctx, ctx->main.stream, "apply_mixed", 2.0 * C * C * npix, 8.0 * C * npix + 4.0 * K * npix);
+  HIPCHK(ctx, launch_apply_mixed(feat, C, npix, wts, K, M, b, out, ctx->wsBlendApply.p, ctx->wsBlendApply.cap, ctx->main.stream));
+  return WCT_OK;
+}
+
+// lambda (host, K values): finite, >= 0, sum > 0 -> lambda / sum (as -styleInterpWeights)
+int normalised_lambda(wct_ctx* ctx, const char* what, int K, const float* lambda, double* out) {
+  if (!lambda) return fail(ctx, WCT_ERR_INVALID, "%s: NULL weights", what);
+  double sum = 0.;
+  for (int k = 0; k < K; ++k) {
+    if (!std::isfinite(lambda[k]) || lambda[k] < 0.f) return fail(ctx, WCT_ERR_INVALID, "%s: weight %d (%g) must be finite and >= 0", what, k, (double)lambda[k]);
+    sum += lambda[k];
+  }
+  if (!(sum > 0.)) return fail(ctx, WCT_ERR_INVALID, "%s: the weights sum to 0", what);
+  for (int k = 0; k < K; ++k) out[k] = lambda[k] / sum;
+  return WCT_OK;
+}
+
+// F = sum_k lam[k] F_k, mu = sum_k lam[k] mu_k into eigS[level] on `st`, then the style-side fold and ev_style[level] (what content_side
+// waits for).  F[k] / mu[k]: device pointers.
+int blend_into_style(wct_ctx* ctx, int level, int K, const double* const* F, const double* const* mu, const double* lam, hipStream_t st) {
+  const size_t C = ctx->mod[WCT_KIND_ENC][level].layers.back().d.cout, cc = C * C;
+  if (int rc = ensure(ctx, ctx->eigS[level], eig_result_bytes((int)C))) return rc;
+  double* res = reinterpret_cast<double*>(ctx->eigS[level].p);
+  {
+    ProfScope ps(ctx, st, "stats_blend", 2.0 * K * (cc + C), 8.0 * (K + 1) * (cc + C));
+    HIPCHK(ctx, launch_stats_blend((int)C, K, F, mu, lam, res + eig_result_F_offset(C), res + cc + C, st));
+  }
+  if (int rc = style_fold(ctx, level, st)) return rc;
+  HIPCHK(ctx, hipEventRecord(ctx->ev_style[level], st));
+  return WCT_OK;
+}
+
+// style side of one level of wct_stylize_interp: the K style sides into eigR[k][level], then their blend into eigS[level] (side lane)
+int interp_style_side(wct_ctx* ctx, int level, int K, const float* const* styles, const int* Hs, const int* Ws, const double* lam) {
+  for (int k = 0; k < K; ++k)
+    if (int rc = style_side_slot(ctx, level, k, styles[k], Hs[k], Ws[k])) return rc;
+  const size_t C = ctx->mod[WCT_KIND_ENC][level].layers.back().d.cout, cc = C * C;
+  const double* F[REG_MAX];
+  const double* mu[REG_MAX];
+  for (int k = 0; k < K; ++k) {
+    const double* r = reinterpret_cast<const double*>(ctx->eigR[k][level].p);
+    F[k] = r + eig_result_F_offset(C);
+    mu[k] = r + cc + C;
+  }
+  Lane& ln = ctx->overlap ? ctx->side : ctx->main;
+  return blend_into_style(ctx, level, K, F, mu, lam, ln.stream);
+}
+
+int multi_style_args(wct_ctx* ctx, const char* what, const float* content, int H, int W, int K, const float* const* styles, const int* Hs,
+                     const int* Ws, int num_run, const float* out) {
+  if (!content || !styles || !Hs || !Ws || !out || num_run < 1) return fail(ctx, WCT_ERR_INVALID, "%s: bad arguments", what);
+  if (K < 1 || K > REG_MAX) return fail(ctx, WCT_ERR_INVALID, "%s: K=%d outside [1, %d]", what, K, REG_MAX);
+  for (int k = 0; k < K; ++k)
+    if (!styles[k]) return fail(ctx, WCT_ERR_INVALID, "%s: style %d is NULL", what, k);
+  for (int level = 1; level <= 5; ++level)
+    if (!ctx->mod[WCT_KIND_ENC][level].loaded || !ctx->mod[WCT_KIND_DEC][level].loaded) return fail(ctx, WCT_ERR_STATE, "%s: level %d not loaded", what, level);
+  if (H < 32 || W < 32) return fail(ctx, WCT_ERR_INVALID, "%s: content %dx%d too small for level 5", what, H, W);
+  return WCT_OK;
+}
+
+// geometry of a weights call (as RegionPlan): level L's map is h[L] x w[L], its K pooled weight maps live at blendW + off[L] (floats);
+// V1[L][k], V2[L][k] read back once
+struct BlendPlan {
+  int h[6], w[6];
+  size_t off[6];
+  double V1[6][REG_MAX], V2[6][REG_MAX];
+};
+constexpr size_t BLEND_STAT_BYTES = 6 * REG_MAX * 2 * sizeof(double) + 4 * sizeof(unsigned);
+
+// one level of the weights cascade on the main lane: encoder (fp32 NHWC) -> weighted moments -> one content solve per active k (n_eff =
+// V1^2 / V2 with sums scaled by V1 / V2: the solver's (sumsq - n mu mu^T) / (n - 1) is then the reliability-weighted covariance) ->
+// mixed apply -> the decoder with its unfolded first conv
+int blend_level(wct_ctx* ctx, int level, const float* img, int H, int W, const BlendPlan& pl, int K, const float* alpha, float* dst) {
+  Module& me = ctx->mod[WCT_KIND_ENC][level];
+  const int C = me.layers.back().d.cout;
+  int h, w;
+  level_dims(level, H, W, h, w);
+  if (h != pl.h[level] || w != pl.w[level]) return fail(ctx, WCT_ERR_INVALID, "stylize_blend: level %d map %dx%d, planned %dx%d", level, h, w, pl.h[level], pl.w[level]);
+  Lane& ln = ctx->main;
+  const size_t fbytes = (size_t)h * w * C * sizeof(float), cc = (size_t)C * C;
+  if (int rc = ensure(ctx, ctx->featC, fbytes)) return rc;
+  if (int rc = ensure(ctx, ctx->regFeat, fbytes)) return rc;
+  if (int rc = ensure(ctx, ctx->regSums, (size_t)K * (C + cc) * sizeof(double))) return rc;
+  if (int rc = ensure(ctx, ctx->regMb, (size_t)K * (cc + C) * sizeof(double))) return rc;
+  SumsView sv;
+  if (int rc = sums_view(ctx, ln, sv)) return rc;
+  float* fC = reinterpret_cast<float*>(ctx->featC.p);
+  float* fO = reinterpret_cast<float*>(ctx->regFeat.p);
+  double* sum = reinterpret_cast<double*>(ctx->regSums.p);
+  double* sumsq = sum + (size_t)K * C;
+  double* M = reinterpret_cast<double*>(ctx->regMb.p);
+  double* b = M + (size_t)K * cc;
+  const float* wl = reinterpret_cast<const float*>(ctx->blendW.p) + pl.off[level];
+  if (int rc = encode_impl(ctx, ln, level, img, H, W, fC, nullptr, nullptr)) return rc;
+  if (int rc = moments_weighted_impl(ctx, ln, fC, C, h, w, wl, K, sum, sumsq)) return rc;
+  unsigned ident = 0;
+  double f[REG_MAX];
+  for (int k = 0; k < K; ++k) {
+    const double v1 = pl.V1[level][k], v2 = pl.V2[level][k];
+    const bool active = v1 > 0. && v2 > 0. && v1 * v1 / v2 >= 2.;
+    f[k] = active ? v1 / v2 : 1.;
+    if (!active) ident |= 1u << k;
+  }
+  HIPCHK(ctx, launch_scale_sums(sum, sumsq, C, K, f, ln.stream));
+  for (int k = 0; k < K; ++k) {
+    if (ident >> k & 1u) continue;
+    const double v1 = pl.V1[level][k], v2 = pl.V2[level][k];
+    if (int rc = eig_impl(ctx, ln, C, v1 * v1 / v2, sum + (size_t)k * C, sumsq + k * cc, 1, ctx->eigCR[k], sv.info)) return rc;
+  }
+  HIPCHK(ctx, hipStreamWaitEvent(ln.stream, ctx->ev_style[level], 0));
+  for (int k = 0; k < K; ++k)
+    if (!(ident >> k & 1u))
+      if (int rc = assemble_impl(ctx, C, ctx->eigCR[k], ctx->eigR[k][level], alpha[k], M + k * cc, b + (size_t)k * C)) return rc;
+  HIPCHK(ctx, launch_mb_identity(M, b, C, K, ident, ln.stream));
+  if (int rc = apply_mixed_impl(ctx, fC, C, (long)h * w, wl, K, M, b, fO)) return rc;
+  return decode_impl(ctx, level, fO, h, w, nullptr, dst);
+}
+}  // namespace
+
+extern "C" {
+
+int wct_moments_weighted(wct_ctx* ctx, const float* feat, int C, int h, int w, const float* weights, int K, double* sum, double* sumsq) {
+  if (!ctx) return WCT_ERR_INVALID;
+  WCT_GUARD(ctx);
+  if (!feat || !weights || !sum || !sumsq) return fail(ctx, WCT_ERR_INVALID, "moments_weighted: NULL pointer");
+  if (int rc = labeled_args(ctx, "moments_weighted", C, h, w, K)) return rc;
+  return moments_weighted_impl(ctx, ctx->main, feat, C, h, w, weights, K, sum, sumsq);
+}
+
+int wct_apply_mixed(wct_ctx* ctx, const float* feat, int C, int h, int w, int layout, const float* weights, int K, const double* M,
+                    const double* b, float* out) {
+  if (!ctx) return WCT_ERR_INVALID;
+  WCT_GUARD(ctx);
+  if (!feat || !weights || !M || !b || !out) return fail(ctx, WCT_ERR_INVALID, "apply_mixed: NULL pointer");
+  if (int rc = labeled_args(ctx, "apply_mixed", C, h, w, K)) return rc;
+  const long npix = (long)h * w;
+  if (layout == WCT_LAYOUT_NHWC) return apply_mixed_impl(ctx, feat, C, npix, weights, K, M, b, out);
+  if (layout != WCT_LAYOUT_NCHW) return fail(ctx, WCT_ERR_INVALID, "apply_mixed: bad layout %d", layout);
+  const size_t fbytes = (size_t)npix * C * sizeof(float);
+  if (int rc = ensure(ctx, ctx->tmpT, 2 * fbytes)) return rc;
+  float* t0 = reinterpret_cast<float*>(ctx->tmpT.p);
+  float* t1 = t0 + (size_t)npix * C;
+  HIPCHK(ctx, launch_nchw_to_nhwc(feat, t0, C, (int)npix, ctx->main.stream));
+  if (int rc = apply_mixed_impl(ctx, t0, C, npix, weights, K, M, b, t1)) return rc;
+  HIPCHK(ctx, launch_nhwc_to_nchw(t1, out, C, (int)npix, ctx->main.stream));
+  return WCT_OK;
+}
+
+int wct_style_blend(wct_ctx* ctx, int level, int K, const double* stats, const float* lambda) {
+  if (!ctx) return WCT_ERR_INVALID;
+  WCT_GUARD(ctx);
+  if (!valid_level(level) || !stats) return fail(ctx, WCT_ERR_INVALID, "style_blend: bad arguments");
+  if (K < 1 || K > REG_MAX) return fail(ctx, WCT_ERR_INVALID, "style_blend: K=%d outside [1, %d]", K, REG_MAX);
+  double lam[REG_MAX];
+  if (int rc = normalised_lambda(ctx, "style_blend", K, lambda, lam)) return rc;
+  Module& me = ctx->mod[WCT_KIND_ENC][level];
+  if (!me.loaded) return fail(ctx, WCT_ERR_STATE, "encoder %d not loaded", level);
+  const size_t C = me.layers.back().d.cout, cc = C * C;
+  const double* F[REG_MAX];
+  const double* mu[REG_MAX];
+  for (int k = 0; k < K; ++k) {
+    F[k] = stats + (size_t)k * (cc + C);
+    mu[k] = F[k] + cc;
+  }
+  return blend_into_style(ctx, level, K, F, mu, lam, ctx->main.stream);
+}
+
+int wct_stylize_interp(wct_ctx* ctx, const float* content, int H, int W, int K, const float* const* styles, const int* Hs, const int* Ws,
+                       const float* lambda, float alpha, int num_run, float* out, int* Ho, int* Wo) {
+  if (!ctx) return WCT_ERR_INVALID;
+  WCT_GUARD(ctx);
+  if (int rc = multi_style_args(ctx, "stylize_interp", content, H, W, K, styles, Hs, Ws, num_run, out)) return rc;
+  if (!std::isfinite(alpha)) return fail(ctx, WCT_ERR_INVALID, "stylize_interp: alpha is not finite");
+  double lam[REG_MAX];
+  if (int rc = normalised_lambda(ctx, "stylize_interp", K, lambda, lam)) return rc;
+  if (int rc = with_deferred_solves(ctx, false, [&]() -> int {
+        if (int rc = fork_side(ctx)) return rc;
+        if (int rc = interp_style_side(ctx, 5, K, styles, Hs, Ws, lam)) return rc;
+        // as cascade(): `out` doubles as the running image; the blended slot of level L - 1 is enqueued behind level L's content side
+        const size_t img_bytes = (size_t)3 * H * W * sizeof(float);
+        if (int rc = ensure(ctx, ctx->tmpT, img_bytes)) return rc;
+        float* bufs[2] = {reinterpret_cast<float*>(ctx->tmpT.p), out};
+        const float* cur = content;
+        int h = H, w = W, which = (5 * num_run) & 1;
+        for (int run = 0; run < num_run; ++run)
+          for (int level = 5; level >= 1; --level) {
+            int ho, wo;
+            float* dst = bufs[which];
+            if (int rc = content_side(ctx, level, cur, h, w, alpha, dst, &ho, &wo)) return rc;
+            if (run == 0 && level > 1)
+              if (int rc = interp_style_side(ctx, level - 1, K, styles, Hs, Ws, lam)) return rc;
+            cur = dst; h = ho; w = wo; which ^= 1;
+          }
+        if (cur != out) HIPCHK(ctx, hipMemcpyAsync(out, cur, (size_t)3 * h * w * sizeof(float), hipMemcpyDeviceToDevice, ctx->main.stream));
+        if (Ho) *Ho = h;
+        if (Wo) *Wo = w;
+        return WCT_OK;
+      })) return rc;
+  return range_readback(ctx);
+}
+
+int wct_stylize_blend(wct_ctx* ctx, const float* content, int H, int W, const float* weights, int K, const float* const* styles, const int* Hs,
+                      const int* Ws, const float* alpha, int num_run, float* out, int* Ho, int* Wo) {
+  if (!ctx) return WCT_ERR_INVALID;
+  WCT_GUARD(ctx);
+  if (!weights || !alpha) return fail(ctx, WCT_ERR_INVALID, "stylize_blend: bad arguments");
+  if (int rc = multi_style_args(ctx, "stylize_blend", content, H, W, K, styles, Hs, Ws, num_run, out)) return rc;
+  for (int k = 0; k < K; ++k)
+    if (!std::isfinite(alpha[k])) return fail(ctx, WCT_ERR_INVALID, "stylize_blend: alpha[%d] is not finite", k);
+  // the pooled weight maps of the five levels, their (V1, V2) and the weight check, read back ONCE: the solvers take each style's
+  // n_eff on the host, and the weights are checked before anything is written to `out`
+  BlendPlan pl{};
+  size_t total = 0;
+  for (int level = 5; level >= 1; --level) {
+    pl.h[level] = (H >> 4) << (5 - level);
+    pl.w[level] = (W >> 4) << (5 - level);
+    pl.off[level] = total;
+    total += ((size_t)K * pl.h[level] * pl.w[level] + 63) & ~(size_t)63;
+  }
+  if (int rc = ensure(ctx, ctx->blendW, total * sizeof(float))) return rc;
+  if (int rc = ensure(ctx, ctx->blendStat, BLEND_STAT_BYTES)) return rc;
+  if (int rc = ensure(ctx, ctx->wsBlendPool, weights_levels_workspace_bytes(H, W))) return rc;
+  if (!ctx->blend_host) HIPCHK(ctx, hipHostMalloc(&ctx->blend_host, BLEND_STAT_BYTES, hipHostMallocDefault));
+  float* maps[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  for (int level = 1; level <= 5; ++level) maps[level] = reinterpret_cast<float*>(ctx->blendW.p) + pl.off[level];
+  double* vv = reinterpret_cast<double*>(ctx->blendStat.p);
+  unsigned* cnt = reinterpret_cast<unsigned*>(vv + 6 * REG_MAX * 2);
+  {
+    ProfScope ps(ctx, ctx->main.stream, "weights_levels", 0, 4.0 * K * H * W * 6 + 4.0 * total);
+    HIPCHK(ctx, launch_weights_levels(weights, H, W, K, pl.h, pl.w, maps, vv, cnt, ctx->wsBlendPool.p, ctx->wsBlendPool.cap, ctx->main.stream));
+  }
+  HIPCHK(ctx, hipMemcpyAsync(ctx->blend_host, ctx->blendStat.p, BLEND_STAT_BYTES, hipMemcpyDeviceToHost, ctx->main.stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->main.stream));
+  const double* hv = reinterpret_cast<const double*>(ctx->blend_host);
+  const unsigned* hc = reinterpret_cast<const unsigned*>(hv + 6 * REG_MAX * 2);
+  if (hc[0]) return fail(ctx, WCT_ERR_INVALID, "stylize_blend: %u weight value(s) are not finite", hc[0]);
+  if (hc[1]) return fail(ctx, WCT_ERR_INVALID, "stylize_blend: %u weight value(s) lie outside [0, 1]", hc[1]);
+  if (hc[2]) return fail(ctx, WCT_ERR_INVALID, "stylize_blend: at %u pixel(s) the weights sum to more than 1", hc[2]);
+  for (int level = 1; level <= 5; ++level)
+    for (int k = 0; k < K; ++k) {
+      pl.V1[level][k] = hv[((size_t)level * REG_MAX + k) * 2];
+      pl.V2[level][k] = hv[((size_t)level * REG_MAX + k) * 2 + 1];
+    }
+  if (int rc = with_deferred_solves(ctx, false, [&]() -> int {
+        if (int rc = fork_side(ctx)) return rc;
+        for (int k = 0; k < K; ++k)
+          if (int rc = style_side_slot(ctx, 5, k, styles[k], Hs[k], Ws[k])) return rc;
+        const size_t img_bytes = (size_t)3 * H * W * sizeof(float);
+        if (int rc = ensure(ctx, ctx->tmpT, img_bytes)) return rc;
+        float* bufs[2] = {reinterpret_cast<float*>(ctx->tmpT.p), out};
+        const float* cur = content;
+        int h = H, w = W, which = (5 * num_run) & 1;
+        for (int run = 0; run < num_run; ++run)
+          for (int level = 5; level >= 1; --level) {
+            float* dst = bufs[which];
+            if (int rc = blend_level(ctx, level, cur, h, w, pl, K, alpha, dst)) return rc;
             if (run == 0 && level > 1)
               for (int k = 0; k < K; ++k)
                 if (int rc = style_side_slot(ctx, level - 1, k, styles[k], Hs[k], Ws[k])) return rc;

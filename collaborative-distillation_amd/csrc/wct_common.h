@@ -207,3 +207,26 @@ size_t apply_labeled_workspace_bytes(int C, int K);
 hipError_t launch_apply_labeled(const float* feat, int C, long npix, const uint8_t* lab, int K, const double* M, const double* b,
                                 float* out, void* workspace, size_t workspace_bytes, hipStream_t s);
 hipError_t launch_mb_identity(double* M, double* b, int C, int K, unsigned mask, hipStream_t s);
+
+// ---- style interpolation and per-pixel style weights (blend.hip); K <= 8
+//   launch_stats_blend       Fo = sum_k lam[k] F[k], muo = sum_k lam[k] mu[k] (C x C and C doubles; device pointers in host arrays), fixed
+//                            k order: lam = (1, 0, ...) reproduces slot 0 bit for bit
+//   launch_weights_levels    from w[K][H][W] (fp32): out[L] = [K][h[L] * wd[L]] area means over each level-L pixel's 2^(L-1) square window
+//                            (L = 1..5), vv[L][8][2] = (V1, V2) = (sum w, sum w^2) of each pooled map (fp64, fixed order), cnt[0..2] =
+//                            non-finite weights, finite weights outside [0, 1], pixels with sum_k w > 1 + 1e-6 (cnt: 4 device words)
+//   launch_moments_weighted  sum[K][C] = sum_p w_k x, sumsq[K][C][C] = sum_p w_k x x^T (fp64) of an NHWC map, w [K][npix]; f32_products
+//                            as launch_moments; bitwise reproducible
+//   launch_apply_mixed       out_p = x_p + sum_k w_k(p) ((M_k x_p + b_k) - x_p) (fp64 maps used in fp32)
+//   launch_scale_sums        sum_k, sumsq_k *= f[k] (f: host array)
+hipError_t launch_stats_blend(int C, int K, const double* const* F, const double* const* mu, const double* lam, double* Fo, double* muo,
+                              hipStream_t s);
+size_t weights_levels_workspace_bytes(int H, int W);
+hipError_t launch_weights_levels(const float* w, int H, int W, int K, const int* h, const int* wd, float* const* out, double* vv,
+                                 unsigned* cnt, void* workspace, size_t workspace_bytes, hipStream_t s);
+size_t moments_weighted_workspace_bytes(int C, long npix, int K);
+hipError_t launch_moments_weighted(const float* feat, int C, long npix, const float* w, int K, double* sum, double* sumsq,
+                                   void* workspace, size_t workspace_bytes, hipStream_t s, bool f32_products);
+size_t apply_mixed_workspace_bytes(int C, int K);
+hipError_t launch_apply_mixed(const float* feat, int C, long npix, const float* w, int K, const double* M, const double* b, float* out,
+                              void* workspace, size_t workspace_bytes, hipStream_t s);
+hipError_t launch_scale_sums(double* sum, double* sumsq, int C, int K, const double* f, hipStream_t s);

@@ -21,6 +21,7 @@ is no CPU fallback.
 from __future__ import annotations
 
 import argparse
+import math
 import os
 import sys
 import time
@@ -59,6 +60,15 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--maskPath", type=str, default=None,
                    help="folder of label maps: content X.* uses DIR/X.png (mode L or P, pixel value = index into --region_styles, 255 = unstyled)")
     p.add_argument("--region_styles", type=str, default=None, help="comma-separated style images of the regions (with --maskPath)")
+    # not in the reference: style interpolation (wct_stylize_interp) and per-pixel style weights (wct_stylize_blend)
+    p.add_argument("--interp_styles", type=str, default=None,
+                   help="comma-separated style images (1 to 8): every content is stylised with their blend (--interp_weights) or, with "
+                        "--weightPath, with per-pixel weights")
+    p.add_argument("--interp_weights", type=str, default=None,
+                   help="comma-separated weights, one per --interp_styles image (>= 0, normalised to sum 1)")
+    p.add_argument("--weightPath", type=str, default=None,
+                   help="folder of weight maps: content X.* uses DIR/X_0.png .. DIR/X_{K-1}.png (mode L, weight = value / 255, "
+                        "summing to <= 1 at every pixel; the rest stays unstyled)")
     return p
 
 
@@ -197,6 +207,128 @@ def check_region_args(args) -> None:
         n = len([p for p in args.region_styles.split(",") if p])
         if not 1 <= n <= 8:
             raise ValueError("--region_styles: 1 to 8 style images, got %d" % n)
+
+
+def interp_style_list(args) -> List[str]:
+    return [p for p in args.interp_styles.split(",") if p]
+
+
+def interp_weight_list(args) -> List[float]:
+    """--interp_weights as floats."""
+    return [float(v) for v in args.interp_weights.split(",") if v.strip()]
+
+
+def check_interp_args(args) -> None:
+    if args.interp_styles is None:
+        if args.interp_weights is not None:
+            raise ValueError("--interp_weights needs --interp_styles")
+        if args.weightPath is not None:
+            raise ValueError("--weightPath needs --interp_styles")
+        return
+    if args.maskPath is not None:
+        raise ValueError("--interp_styles does not mix with --maskPath")
+    n = len(interp_style_list(args))
+    if not 1 <= n <= 8:
+        raise ValueError("--interp_styles: 1 to 8 style images, got %d" % n)
+    if args.weightPath is not None:
+        if args.interp_weights is not None:
+            raise ValueError("--interp_weights does not mix with --weightPath (the weight maps are the weights)")
+        return
+    if args.interp_weights is None:
+        raise ValueError("--interp_styles goes with --interp_weights (one weight per style) or --weightPath (weight maps)")
+    try:
+        lam = interp_weight_list(args)
+    except ValueError:
+        raise ValueError("--interp_weights: comma-separated numbers expected, got %r" % args.interp_weights) from None
+    if len(lam) != n:
+        raise ValueError("--interp_weights: one weight per style image: %d styles, %d weights" % (n, len(lam)))
+    if any(not math.isfinite(v) or v < 0 for v in lam) or not sum(lam) > 0:
+        raise ValueError("--interp_weights: weights must be finite and >= 0 with a positive sum, got %s" % args.interp_weights)
+
+
+def weight_jobs(content_dir: str, weight_dir: str, K: int, content_mark: str = ".") -> List[Tuple[str, List[str]]]:
+    """--weightPath: every content X.* (listdir order, --picked_content_mark) with its K weight maps DIR/X_k.png (X = text before the
+    first dot, as pair_name); a missing map is an error that names the file."""
+    jobs = []
+    for c in os.listdir(content_dir):
+        if not (is_image_file(c) and content_mark in c):
+            continue
+        stem = c.split(".")[0]
+        maps = [os.path.join(weight_dir, "%s_%d.png" % (stem, k)) for k in range(K)]
+        for m in maps:
+            if not os.path.isfile(m):
+                raise FileNotFoundError("weight map %s for content %s not found" % (m, c))
+        jobs.append((c, maps))
+    return jobs
+
+
+def load_weights(paths: List[str], shape: Tuple[int, int]):
+    """K weight maps as float32 K x H x W: mode L PNGs, weight = value / 255, at the content's size after --content_size (`shape`);
+    never resampled."""
+    import numpy as np
+    from PIL import Image
+    out = np.empty((len(paths),) + tuple(shape), np.float32)
+    for k, path in enumerate(paths):
+        img = Image.open(path)
+        if img.mode != "L":
+            raise ValueError("weight map %s has mode %s; expected L (weight = value / 255)" % (path, img.mode))
+        a = np.array(img, dtype=np.uint8)
+        if tuple(a.shape) != tuple(shape):
+            raise ValueError("weight map %s is %dx%d (HxW) but the content is %dx%d after --content_size; weight maps are not resampled"
+                             % (path, a.shape[0], a.shape[1], shape[0], shape[1]))
+        out[k] = a.astype(np.float32) / np.float32(255)
+    return out
+
+
+def interp_out_name(args, content_file: str, blend: bool = False) -> str:
+    """<log_mark>_mode=<m>_alpha=<a>_<X>+interp.jpg (+blend.jpg with --weightPath)."""
+    return out_name(args, content_file.split(".")[0] + ("+blend.jpg" if blend else "+interp.jpg"))
+
+
+def run_interp(args, wct, content_dir, logprinter) -> Tuple[float, int]:
+    """--interp_styles: one stylisation per content against the blend of the styles (wct_stylize_interp) or, with --weightPath, with
+    per-pixel weights (wct_stylize_blend); the serial loop.  Returns (total seconds, contents)."""
+    import torch
+    from PIL import Image
+    styles = interp_style_list(args)
+    s_dev = [_to_tensor(wct, torch.from_numpy(load_rgb_u8(p)).cuda(), args.style_size) for p in styles]
+    blend = args.weightPath is not None
+    if blend:
+        jobs = weight_jobs(content_dir, args.weightPath, len(styles), args.picked_content_mark)
+    else:
+        jobs = [(c, None) for c in os.listdir(content_dir) if is_image_file(c) and args.picked_content_mark in c]
+        lam = interp_weight_list(args)
+    logprinter("Number of contents: %s" % len(jobs))
+
+    def run(c_f32, st, wmap):
+        if blend:
+            return wct.stylize_blend(c_f32, st, wmap, args.alpha, args.num_run)
+        return wct.stylize_interp(c_f32, st, lam, args.alpha, args.num_run)
+
+    avg = 0.0
+    for i, (cfile, wpaths) in enumerate(jobs):
+        logprinter("\n" + "*" * 30 + ' #%s: Transferring "%s" by %s' % (i, cfile, "weight maps" if blend else "interpolation"))
+        c_u8 = torch.from_numpy(load_rgb_u8(os.path.join(content_dir, cfile))).pin_memory().cuda(non_blocking=True)
+        wmap = None
+        if blend:
+            H, W = resized_shape(int(c_u8.shape[0]), int(c_u8.shape[1]), args.content_size)
+            wmap = torch.from_numpy(load_weights(wpaths, (H, W))).cuda()
+        t0 = time.time()
+        c_f32 = _to_tensor(wct, c_u8, args.content_size)
+        res = run(c_f32, s_dev, wmap)
+        if wct.saturation_count(reset=True):
+            logprinter("WARNING: f16x3 range exceeded for this content -> recomputing it with exact-fp32 convolutions")
+            wct.set_conv_mode("fp32")
+            s32 = [_to_tensor(wct, torch.from_numpy(load_rgb_u8(p)).cuda(), args.style_size) for p in styles]
+            res = run(c_f32, s32, wmap)
+            wct.sync()
+            wct.set_conv_mode("f16x3")
+        out = wct.to_u8(res, args.round_mode).cpu().numpy()
+        Image.fromarray(out).save(interp_out_name(args, cfile, blend))
+        dt = time.time() - t0
+        avg += dt
+        logprinter("Elapsed time is: %.4f seconds" % dt)
+    return avg, len(jobs)
 
 
 class LogPrinter:     # WCT.py:78-82
@@ -403,6 +535,7 @@ def main(argv: Optional[List[str]] = None) -> int:
     args = build_parser().parse_args(argv)
     checkpoint_args(args)
     check_region_args(args)
+    check_interp_args(args)
     if args.synthesis:
         raise NotImplementedError("--synthesis is broken in the reference (data_loader.py:74) and not part of this path")
     os.makedirs(args.outf, exist_ok=True)
@@ -420,6 +553,15 @@ def main(argv: Optional[List[str]] = None) -> int:
         avg = run_regions(args, wct, content_dir, logprinter)
         if jobs:
             logprinter("Processed %d images. Average processing time per image is: %.4f seconds" % (len(jobs), avg / len(jobs)))
+        return 0
+    if args.interp_styles is not None:
+        from .wct import WCT
+        wct = WCT(args)
+        if args.pipeline > 0:
+            logprinter("--pipeline is ignored with --interp_styles: interpolation and weight-map runs use the serial loop")
+        avg, n = run_interp(args, wct, content_dir, logprinter)
+        if n:
+            logprinter("Processed %d images. Average processing time per image is: %.4f seconds" % (n, avg / n))
         return 0
     pairs = list_pairs(content_dir, style_dir, args.picked_content_mark, args.picked_style_mark)
 

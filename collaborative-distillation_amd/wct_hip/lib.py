@@ -27,6 +27,7 @@ SYMBOLS = [
     "wct_style_prepare_levels", "wct_style_stats_count", "wct_style_export", "wct_style_import", "wct_stylize_prepared",
     "wct_u8_to_planar", "wct_planar_to_u8", "wct_stylize_u8", "wct_resize_shape", "wct_resize_u8", "wct_resize_u8_to_planar",
     "wct_moments_labeled", "wct_apply_labeled", "wct_stylize_regions",
+    "wct_stylize_interp", "wct_style_blend", "wct_stylize_blend", "wct_moments_weighted", "wct_apply_mixed",
     "wct_workspace_bytes", "wct_reserve", "wct_set_conv_mode", "wct_set_numpy_variant", "wct_set_overlap", "wct_profile_enable", "wct_profile_reset", "wct_profile_read",
 ]
 
@@ -135,6 +136,11 @@ def load() -> ctypes.CDLL:
     lib.wct_moments_labeled.argtypes = [c_void_p, vp, c_int, c_int, c_int, vp, c_int, vp, vp, vp]
     lib.wct_apply_labeled.argtypes = [c_void_p, vp, c_int, c_int, c_int, c_int, vp, c_int, vp, vp, vp]
     lib.wct_stylize_regions.argtypes = [c_void_p, vp, c_int, c_int, vp, c_int, POINTER(c_void_p), ip, ip, fp, c_int, vp, ip, ip]
+    lib.wct_stylize_interp.argtypes = [c_void_p, vp, c_int, c_int, c_int, POINTER(c_void_p), ip, ip, fp, c_float, c_int, vp, ip, ip]
+    lib.wct_style_blend.argtypes = [c_void_p, c_int, c_int, vp, fp]
+    lib.wct_stylize_blend.argtypes = [c_void_p, vp, c_int, c_int, vp, c_int, POINTER(c_void_p), ip, ip, fp, c_int, vp, ip, ip]
+    lib.wct_moments_weighted.argtypes = [c_void_p, vp, c_int, c_int, c_int, vp, c_int, vp, vp]
+    lib.wct_apply_mixed.argtypes = [c_void_p, vp, c_int, c_int, c_int, c_int, vp, c_int, vp, vp, vp]
     lib.wct_u8_to_planar.argtypes = [c_void_p, vp, c_int, c_int, vp]
     lib.wct_planar_to_u8.argtypes = [c_void_p, vp, c_int, c_int, vp, c_int]
     lib.wct_stylize_u8.argtypes = [c_void_p, vp, c_int, c_int, vp, c_int, c_int, c_float, c_int, vp, ip, ip, c_int]

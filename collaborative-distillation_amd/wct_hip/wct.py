@@ -727,6 +727,123 @@ class WCT:
                                                 out.data_ptr(), byref(ho), byref(wo)))
         return out.view(-1)[: 3 * ho.value * wo.value].view(1, 3, ho.value, wo.value)
 
+    # ------------------------------------------------------------------ style interpolation and per-pixel style weights
+    def _styles(self, styles):
+        ss = [self._img(s) for s in styles]
+        K = len(ss)
+        ptrs = (c_void_p * max(K, 1))(*[s.data_ptr() for s in ss])
+        hs = (c_int * max(K, 1))(*[int(s.shape[1]) for s in ss])
+        ws = (c_int * max(K, 1))(*[int(s.shape[2]) for s in ss])
+        return ss, ptrs, hs, ws
+
+    @staticmethod
+    def _lambda(weights, K: int):
+        lam = [float(v) for v in weights]
+        if len(lam) != K:
+            raise ValueError("weights: expected %d values (one per style), got %d" % (K, len(lam)))
+        return (ctypes.c_float * max(K, 1))(*lam)
+
+    def _weight_maps(self, weights: torch.Tensor, K: int, h: int, w: int) -> torch.Tensor:
+        if weights.dtype != torch.float32 or tuple(weights.shape) != (K, h, w):
+            raise ValueError("weights must be a float32 tensor of shape (%d, %d, %d), got %s %s" % (K, h, w, weights.dtype, tuple(weights.shape)))
+        if not weights.is_cuda:
+            raise ValueError("weights must be a CUDA float32 tensor")
+        return weights.to(self.stats_device).contiguous()
+
+    @torch.no_grad()
+    def moments_weighted(self, feat_nhwc: torch.Tensor, weights: torch.Tensor):
+        """Raw fp64 weighted sums of an NHWC feature [1,h,w,C] with K weight maps [K,h,w] (fp32): (sum[K,C], sumsq[K,C,C]),
+        sum[k] = sum_p w_k(p) x_p, sumsq[k] = sum_p w_k(p) x_p x_p^T."""
+        f = self._nhwc(feat_nhwc)
+        h, w, C = (int(v) for v in f.shape)
+        K = int(weights.shape[0]) if weights.dim() == 3 else 0
+        wt = self._weight_maps(weights, K, h, w)
+        s = torch.empty(K, C, device=f.device, dtype=torch.float64)
+        ss = torch.empty(K, C, C, device=f.device, dtype=torch.float64)
+        self._stream()
+        self._chk(self._lib.wct_moments_weighted(self._ctx, f.data_ptr(), C, h, w, wt.data_ptr(), K, s.data_ptr(), ss.data_ptr()))
+        return s, ss
+
+    @torch.no_grad()
+    def apply_mixed(self, feat: torch.Tensor, weights: torch.Tensor, M: torch.Tensor, b: torch.Tensor, layout: str = "nhwc") -> torch.Tensor:
+        """out_p = x_p + sum_k w_k(p) ((M[k] x_p + b[k]) - x_p) with weights [K,h,w] (fp32), M [K,C,C], b [K,C].  feat is [1,h,w,C] (nhwc)
+        or [1,C,h,w] (nchw); the result has the same shape."""
+        f = feat[0] if feat.dim() == 4 else feat
+        if f.dim() != 3:
+            raise ValueError("expected a feature map [1,h,w,C] / [1,C,h,w], got %s" % (tuple(feat.shape),))
+        f = self._dev_f32(f)
+        nchw = layout == "nchw"
+        if nchw:
+            C, h, w = (int(v) for v in f.shape)
+        else:
+            h, w, C = (int(v) for v in f.shape)
+        K = int(b.shape[0]) if b.dim() == 2 else int(b.numel()) // C
+        wt = self._weight_maps(weights, K, h, w)
+        M, b = self._dev_f64(M, K * C * C, "M"), self._dev_f64(b, K * C, "b")
+        out = torch.empty((1,) + tuple(f.shape), device=f.device, dtype=torch.float32)
+        self._stream()
+        self._chk(self._lib.wct_apply_mixed(self._ctx, f.data_ptr(), C, h, w, _lib.LAYOUT_NCHW if nchw else _lib.LAYOUT_NHWC,
+                                            wt.data_ptr(), K, M.data_ptr(), b.data_ptr(), out.data_ptr()))
+        return out
+
+    @torch.no_grad()
+    def stylize_interp(self, contentImg: torch.Tensor, styles, weights, alpha: Optional[float] = None, num_run: int = 1,
+                       out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Style interpolation (-styleInterpWeights): csF = alpha sum_k l_k WCT(cF, style_k) + (1 - alpha) cF at every level, with
+        l = weights / sum(weights) (one finite weight >= 0 per style, sum > 0)."""
+        alpha = self.alpha if alpha is None else float(alpha)
+        c = self._img(contentImg)
+        H, W = int(c.shape[1]), int(c.shape[2])
+        ss, ptrs, hs, ws = self._styles(styles)
+        K = len(ss)
+        lam = self._lambda(weights, K)
+        out = self._out_image(out, H, W)
+        ho, wo = c_int(), c_int()
+        self._stream()
+        self._chk(self._lib.wct_stylize_interp(self._ctx, c.data_ptr(), H, W, K, ptrs, hs, ws, lam, alpha, int(num_run),
+                                               out.data_ptr(), byref(ho), byref(wo)))
+        return out.view(-1)[: 3 * ho.value * wo.value].view(1, 3, ho.value, wo.value)
+
+    def style_blend(self, stats_per_style, weights, levels=(5, 4, 3, 2, 1)):
+        """Blend cached style statistics into the context (as style_import): stats_per_style[k][L] is style k's style_export(L);
+        the context then holds sum_k l_k stats_k for each level L in `levels` (l = weights / sum(weights)).  stylize_prepared follows."""
+        K = len(stats_per_style)
+        lam = self._lambda(weights, K)
+        self._stream()
+        for L in levels:
+            n = c_size_t()
+            self._chk(self._lib.wct_style_stats_count(self._ctx, int(L), byref(n)))
+            parts = [st[L] for st in stats_per_style]
+            for p in parts:
+                if p.dtype != torch.float64 or not p.is_cuda or p.numel() != n.value:
+                    raise ValueError("style_blend: level %d expects %d fp64 values on the GPU per style" % (L, n.value))
+            buf = torch.stack([p.to(self.stats_device).reshape(-1) for p in parts]).contiguous()
+            self._blend_keep = buf     # read by the blend launch on the context's stream
+            self._chk(self._lib.wct_style_blend(self._ctx, int(L), K, buf.data_ptr(), lam))
+
+    @torch.no_grad()
+    def stylize_blend(self, contentImg: torch.Tensor, styles, weights_map: torch.Tensor, alpha=None, num_run: int = 1,
+                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The cascade with per-pixel style weights: `weights_map` (float32 [K, H, W], CUDA) gives each content pixel a weight in [0, 1]
+        per style, summing to <= 1 (the rest stays unstyled); `alpha` is one float or one per style."""
+        c = self._img(contentImg)
+        H, W = int(c.shape[1]), int(c.shape[2])
+        ss, ptrs, hs, ws = self._styles(styles)
+        K = len(ss)
+        if alpha is None:
+            alpha = self.alpha
+        al = [float(alpha)] * K if isinstance(alpha, (int, float)) else [float(a) for a in alpha]
+        if len(al) != K:
+            raise ValueError("alpha: expected 1 or %d values, got %d" % (K, len(al)))
+        wt = self._weight_maps(weights_map, K, H, W)
+        out = self._out_image(out, H, W)
+        av = (ctypes.c_float * max(K, 1))(*al)
+        ho, wo = c_int(), c_int()
+        self._stream()
+        self._chk(self._lib.wct_stylize_blend(self._ctx, c.data_ptr(), H, W, wt.data_ptr(), K, ptrs, hs, ws, av, int(num_run),
+                                              out.data_ptr(), byref(ho), byref(wo)))
+        return out.view(-1)[: 3 * ho.value * wo.value].view(1, 3, ho.value, wo.value)
+
     def set_conv_mode(self, mode: str):
         """'f16x3' (default: split-f16 MFMA, fp32-class accuracy) or 'fp32' (exact fp32 MFMA)."""
         self._chk(self._lib.wct_set_conv_mode(self._ctx, {"fp32": 0, "f16x3": 1}[mode]))

@@ -325,6 +325,38 @@ int wct_apply_labeled(wct_ctx* ctx, const float* feat, int C, int h, int w, int 
 int wct_stylize_regions(wct_ctx* ctx, const float* content, int H, int W, const uint8_t* labels, int K, const float* const* styles,
                         const int* Hs, const int* Ws, const float* alpha, int num_run, float* out, int* Ho, int* Wo);
 
+/* Style interpolation and per-pixel style weights, 1 <= K <= 8 styles.  whiten_and_color (util_wct.py:62-131) is linear in the style
+ * statistics: with S_k = cov_s,k^(1/2) and Wc = cov_c^(-1/2), sum_k l_k (S_k Wc (x - mu_c) + mu_s,k) = (sum_k l_k S_k) Wc (x - mu_c) + sum_k
+ * l_k mu_s,k, so interpolation (the WCT paper's third user control, -styleInterpWeights) is ONE blended style slot per level.
+ *   wct_stylize_interp   extends wct_stylize: csF = alpha sum_k l_k whiten_and_color(cF, e_L(style_k)) + (1 - alpha) cF at every level,
+ *                        l = lambda / sum(lambda) (lambda: K HOST floats, finite, >= 0, sum > 0).  The K style sides of a level run on the
+ *                        side stream into K slots, one launch blends them (fixed k order: lambda = (1, 0, ..) gives style 0's statistics
+ *                        bit for bit), then the unchanged single-style content path.  styles: device pointers in a HOST array.
+ *   wct_style_blend      the same blend of K stat sets in wct_style_export layout (device, K * wct_style_stats_count doubles, one set
+ *                        after the other) into the context's style statistics of `level` (as wct_style_import): cached styles cost one
+ *                        small launch per level before wct_stylize_prepared.
+ *   wct_stylize_blend    per-pixel weights: weights K x H x W (device fp32), each in [0, 1] and sum_k <= 1 at every pixel (the rest is
+ *                        unstyled content), alpha[K] (HOST).  Level L uses w_k,L = the mean of w_k over each feature pixel's 2^(L-1)
+ *                        square window; per k the content statistics are reliability-weighted: mu_k = sum w x / V1, cov_k = sum w (x -
+ *                        mu_k)(x - mu_k)^T / (V1 - V2 / V1) (V1 = sum w_k,L, V2 = sum w_k,L^2); style k is active at a level iff V1 > 0
+ *                        and V1^2 / V2 >= 2; csF(p) = x_p + sum_{k active} w_k,L(p) alpha_k (target_k(x_p) - x_p).  Constant weights
+ *                        are wct_stylize_interp, 0/1 weights constant on aligned 16 x 16 blocks are wct_stylize_regions.  The call reads
+ *                        (V1, V2) and the weight check back ONCE at its start (one stream synchronisation), so it cannot be captured into
+ *                        a HIP graph.  Non-finite weights, weights outside [0, 1] or a pixel whose weights sum to more than 1 + 1e-6
+ *                        return WCT_ERR_INVALID before anything is written to out (wct_last_error says which).
+ *   wct_moments_weighted per k: sum[k*C + c] = sum_p w_k(p) x_p[c], sumsq[k*C*C + a*C + b] = sum_p w_k(p) x_p[a] x_p[b] (device f64) of an
+ *                        NHWC map, weights K x h x w (device fp32).  Arithmetic classes of wct_moments_labeled; bitwise reproducible.
+ *   wct_apply_mixed      out_p = x_p + sum_k w_k(p) ((M_k x_p + b_k) - x_p), M [K*C*C], b [K*C] device f64 (used in fp32); layout as
+ *                        wct_apply. */
+int wct_stylize_interp(wct_ctx* ctx, const float* content, int H, int W, int K, const float* const* styles, const int* Hs, const int* Ws,
+                       const float* lambda, float alpha, int num_run, float* out, int* Ho, int* Wo);
+int wct_style_blend(wct_ctx* ctx, int level, int K, const double* stats, const float* lambda);
+int wct_stylize_blend(wct_ctx* ctx, const float* content, int H, int W, const float* weights, int K, const float* const* styles, const int* Hs,
+                      const int* Ws, const float* alpha, int num_run, float* out, int* Ho, int* Wo);
+int wct_moments_weighted(wct_ctx* ctx, const float* feat, int C, int h, int w, const float* weights, int K, double* sum, double* sumsq);
+int wct_apply_mixed(wct_ctx* ctx, const float* feat, int C, int h, int w, int layout, const float* weights, int K, const double* M,
+                    const double* b, float* out);
+
 /* Style statistics cache.  wct_style_prepare leaves, per level, the style mean and cov^(1/2) inside the
  * context; they depend only on the style image, so
  *   wct_stylize_prepared  runs the content cascade against them (no style-side work): content x style batches pay
