@@ -291,6 +291,10 @@ bool l1_capable(const ConvDesc& enc0) {
   return (enc0.flags & CONV_IN_NCHW3) && !(enc0.flags & (CONV_POOL_OUT | CONV_NO_RELU)) && enc0.l1w16 && enc0.cout <= 32 && (enc0.cout % 4) == 0;
 }
 
+// l1_moments_kernel forms the products of channels 0..23 only, and l1_decode_kernel reads the first 8 channels of the second
+// 16-channel chunk only: the two fused kernels are exact for encoders of at most 24 channels (l1_encode_kernel writes all 32)
+bool l1_fusable(const ConvDesc& enc0) { return l1_capable(enc0) && enc0.cout <= 24; }
+
 hipError_t launch_l1_encode(const ConvDesc& e, const float* img, float* out, int H, int W, hipStream_t s) {
   if (!l1_capable(e) || H < 2 || W < 2) return hipErrorInvalidValue;
   L1EncArgs a;
@@ -436,7 +440,7 @@ hipError_t launch_in3_wide(const ConvDesc& e, const float* img, void* out, int H
 
 // dec0: the decoder's only conv with the WCT map folded in (split-f16 packed, 10 taps, cout_pad 16)
 hipError_t launch_l1_decode(const ConvDesc& e, const ConvDesc& dec0, const float* img, float* out, int H, int W, hipStream_t s) {
-  if (!l1_capable(e) || H < 2 || W < 2 || !dec0.wpk16 || !dec0.wph16 || dec0.cout != 3 || dec0.cout_pad != 16 || dec0.cin != e.cout ||
+  if (!l1_fusable(e) || H < 2 || W < 2 || !dec0.wpk16 || !dec0.wph16 || dec0.cout != 3 || dec0.cout_pad != 16 || dec0.cin != e.cout ||
       dec0.cin_chunks != 2 || !(dec0.flags & CONV_OUT_NCHW3) || (dec0.flags & (CONV_UP_IN | CONV_NO_RELU | CONV_POOL_OUT)))
     return hipErrorInvalidValue;
   L1DecArgs a;

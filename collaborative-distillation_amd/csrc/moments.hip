@@ -786,6 +786,9 @@ MomArgs plan(int C, long npix) {
   static const int maxld6 = [] { const char* e = wct_debug_env("WCT_MOM_MAXLD6"); return e ? atoi(e) : 6; }();
   const int maxld = a.pw == 6 ? maxld6 : MAXLD;
   a.MP = std::max(16, std::min(256, (maxld * 256 * 4 / C) / 16 * 16));
+  // pixel split: each wave takes MP / 16 steps of 4 pixels and walks them 4 at a time (tile_steps3) -- MP must be a multiple of 64.
+  // (C = 36 and 40 gave MP = 160 / 144: the waves' step ranges overlapped and the last one read past the tile.)
+  if (a.pixsplit) a.MP = std::max(64, a.MP / 64 * 64);
   const int MP = a.MP;
   a.npix = npix;
   static long npc_target = [] { const char* e = wct_debug_env("WCT_MOM_NPC"); return e ? atol(e) : 512L; }();
@@ -901,7 +904,7 @@ size_t l1_moments_workspace_bytes() { return (size_t)2 * num_cus() * (3 * 256 + 
 
 hipError_t launch_l1_moments(const ConvDesc& e, const float* img, int H, int W, int x0, int x1, double* sum, double* sumsq,
                              void* ws, size_t ws_bytes, hipStream_t s, bool f32_products) {
-  if (!l1_capable(e) || H < 2 || W < 2 || x0 < 0 || x1 > W || x1 <= x0) return hipErrorInvalidValue;
+  if (!l1_fusable(e) || H < 2 || W < 2 || x0 < 0 || x1 > W || x1 <= x0) return hipErrorInvalidValue;
   if (ws_bytes < l1_moments_workspace_bytes()) return hipErrorOutOfMemory;
   L1MomArgs a;
   a.img = img;

@@ -882,7 +882,8 @@ void level_dims(int level, int H, int W, int& h, int& w) {
   for (int i = 1; i < level; ++i) { h /= 2; w /= 2; }
 }
 
-// level 1 of the 16x cascade without relu1_1 in HBM: single-conv encoder (3 -> <= 32) and single-conv decoder (-> 3)
+// level 1 of the 16x cascade without relu1_1 in HBM: single-conv encoder (3 -> 17..24) and single-conv decoder (-> 3).  Wider level-1
+// encoders (25..32) take the layer-wise path: the fused moments and decoder kernels cover 24 channels only (l1_fusable)
 bool l1_fused(const wct_ctx* ctx, int level) {
   if (ctx->conv_mode != 1 || !ctx->fuse || !ctx->l1fuse) return false;
   const Module& me = ctx->mod[WCT_KIND_ENC][level];
@@ -890,7 +891,7 @@ bool l1_fused(const wct_ctx* ctx, int level) {
   if (!me.loaded || !md.loaded || me.layers.size() != 1 || md.layers.size() != 1) return false;
   const ConvDesc& e = me.layers[0].d;
   const ConvDesc& d = md.layers[0].d;
-  return l1_capable(e) && d.cin == e.cout && d.cout == 3 && d.cout_pad == 16 && d.cin_chunks == 2 && (d.flags & CONV_OUT_NCHW3);
+  return l1_fusable(e) && d.cin == e.cout && d.cout == 3 && d.cout_pad == 16 && d.cin_chunks == 2 && (d.flags & CONV_OUT_NCHW3);
 }
 
 int l1_moments_impl(wct_ctx* ctx, Lane& ln, int level, const float* img, int H, int W, int x0, int x1, double* sum, double* sumsq) {
@@ -1217,6 +1218,12 @@ int wct_load_module(wct_ctx* ctx, int kind, int level, int n_layers, const wct_l
     for (int e = 0; e < L.cout; ++e)
       if (!std::isfinite(L.bias[e])) return fail(ctx, WCT_ERR_INVALID, "load_module: layer %d has a non-finite bias", i);
     if (kind == WCT_KIND_ENC && last && L.pool_after) return fail(ctx, WCT_ERR_INVALID, "encoder cannot end in a pool");
+    // shapes no conv kernel runs (launch_conv3x3 / launch_conv3x3_f16 would refuse them at the first encode or decode)
+    if (kind == WCT_KIND_ENC && first && L.cout > 64)
+      return fail(ctx, WCT_ERR_INVALID, "load_module: the first encoder conv has %d output channels; at most 64 are supported", L.cout);
+    if (kind == WCT_KIND_ENC && first && L.pool_after) return fail(ctx, WCT_ERR_INVALID, "load_module: the first encoder conv cannot pool");
+    if (kind == WCT_KIND_ENC && L.up_after) return fail(ctx, WCT_ERR_INVALID, "load_module: encoder layer %d cannot upsample", i);
+    if (kind == WCT_KIND_DEC && L.pool_after) return fail(ctx, WCT_ERR_INVALID, "load_module: decoder layer %d cannot pool", i);
     if (kind == WCT_KIND_DEC && last && L.up_after) return fail(ctx, WCT_ERR_INVALID, "decoder cannot end in an upsample");
   }
   Module& m = ctx->mod[kind][level];

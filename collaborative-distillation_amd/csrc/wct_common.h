@@ -99,7 +99,8 @@ bool conv_fusable_tail(const ConvDesc& d0, const ConvDesc& d1);
 hipError_t launch_enc_head(const ConvDesc& d0, const ConvDesc& d1, const float* img, float* out, int H, int W, hipStream_t s);   // d1.flags & CONV_OUT_SP16
 hipError_t launch_dec_tail(const ConvDesc& d0, const ConvDesc& d1, const float* in, float* out, int H, int W, hipStream_t s);
 // level 1 without materialising relu1_1 (level1.hip, moments.hip)
-bool l1_capable(const ConvDesc& enc0);
+bool l1_capable(const ConvDesc& enc0);   // l1_encode: 3 -> <= 32 channels
+bool l1_fusable(const ConvDesc& enc0);   // l1_moments / l1_decode: 3 -> <= 24 channels
 hipError_t launch_l1_encode(const ConvDesc& enc0, const float* img, float* out, int H, int W, hipStream_t s);
 hipError_t launch_l1_decode(const ConvDesc& enc0, const ConvDesc& dec0_folded, const float* img, float* out, int H, int W, hipStream_t s);
 // the 3 -> 64 first conv of the un-pruned encoders in f16x3 (level1.hip in3_wide_kernel): fp32 NHWC or SP16 out

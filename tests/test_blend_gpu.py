@@ -59,7 +59,7 @@ def _maps(kind, H, W, rng):
 
 
 # ---------------------------------------------------------------------------------------------------- 1. kernels
-@pytest.mark.parametrize("C", [24, 32, 64, 128, 512])
+@pytest.mark.parametrize("C", [24, 32, 64, 128, 512, 4, 20, 36, 132, 260])
 @pytest.mark.parametrize("K", [1, 3, 8])
 @pytest.mark.parametrize("mom32", [0, 1])
 def test_moments_weighted_vs_numpy(torch_cuda, wct16, C, K, mom32):
@@ -90,7 +90,7 @@ def test_moments_weighted_vs_numpy(torch_cuda, wct16, C, K, mom32):
             assert np.array_equal(q, q.T)
 
 
-@pytest.mark.parametrize("C", [24, 64, 128, 512])
+@pytest.mark.parametrize("C", [24, 64, 128, 512, 4, 20, 36, 132, 260])
 @pytest.mark.parametrize("layout", ["nhwc", "nchw"])
 def test_apply_mixed_vs_numpy(torch_cuda, wct16, C, layout):
     torch = torch_cuda

@@ -62,7 +62,7 @@ def _masks(kind, H, W, rng):
 
 
 # ---------------------------------------------------------------------------------------------------- 1. per-label moments
-@pytest.mark.parametrize("C", [24, 32, 64, 128])
+@pytest.mark.parametrize("C", [24, 32, 64, 128, 4, 20, 36, 132, 260])
 @pytest.mark.parametrize("K", [1, 2, 5])
 @pytest.mark.parametrize("mom32", [0, 1])
 def test_moments_labeled_vs_numpy(torch_cuda, wct16, C, K, mom32):
@@ -95,7 +95,7 @@ def test_moments_labeled_vs_numpy(torch_cuda, wct16, C, K, mom32):
 
 
 # ---------------------------------------------------------------------------------------------------- 2. labeled apply
-@pytest.mark.parametrize("C", [24, 64, 128, 512])
+@pytest.mark.parametrize("C", [24, 64, 128, 512, 4, 20, 36, 132, 260])
 @pytest.mark.parametrize("layout", ["nhwc", "nchw"])
 def test_apply_labeled_vs_numpy(torch_cuda, wct16, C, layout):
     torch = torch_cuda
