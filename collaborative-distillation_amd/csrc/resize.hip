@@ -25,6 +25,18 @@ inline double triangle(double x) {
   return x < 1.0 ? 1.0 - x : 0.0;
 }
 
+// Pillow's bicubic_filter (Keys' cubic with a = -0.5, support 2.0): what Image.resize() without a filter argument uses at the
+// reference's Pillow pin -- the texture resize of data_loader.py:72.  Negative lobes: the weights keep their sign through the
+// fixed-point rounding below and the kernels' clip8 clamps overshoot; sum |w| * 255 stays far inside the int32 accumulator.
+inline double bicubic(double x) {
+#pragma clang fp contract(off)   // Pillow's C evaluates these products and sums one by one
+  const double a = -0.5;
+  if (x < 0.0) x = -x;
+  if (x < 1.0) return ((a + 2.0) * x - (a + 3.0)) * x * x + 1;
+  if (x < 2.0) return (((x - 5) * x + 8) * x - 4) * a;
+  return 0.0;
+}
+
 __device__ __forceinline__ unsigned clip8(int v) {
   v >>= PRECISION_BITS;
   return (unsigned)(v < 0 ? 0 : (v > 255 ? 255 : v));
@@ -73,12 +85,14 @@ __global__ void resize_v_kernel(const uint8_t* in, int rowbytes, int oH, int ksi
 
 }  // namespace
 
-// Weight tables of one axis (Pillow's precompute_coeffs + normalize_coeffs_8bpc for the box [0, in_size))
-void resize_axis_tables(int in_size, int out_size, int& ksize, std::vector<int>& bounds, std::vector<int>& kk) {
+// Weight tables of one axis (Pillow's precompute_coeffs + normalize_coeffs_8bpc for the box [0, in_size)); filter: RESIZE_BILINEAR
+// (triangle, support 1) or RESIZE_BICUBIC (support 2).  The kernels above only see taps and weights.
+void resize_axis_tables(int in_size, int out_size, int filter, int& ksize, std::vector<int>& bounds, std::vector<int>& kk) {
+  const bool cubic = filter == RESIZE_BICUBIC;
   const float in0 = 0.f, in1 = (float)in_size;
   double scale = (double)(in1 - in0) / out_size, filterscale = scale;
   if (filterscale < 1.0) filterscale = 1.0;
-  const double support = 1.0 * filterscale;
+  const double support = (cubic ? 2.0 : 1.0) * filterscale;
   ksize = (int)std::ceil(support) * 2 + 1;
   bounds.assign((size_t)out_size * 2, 0);
   kk.assign((size_t)out_size * ksize, 0);
@@ -92,7 +106,7 @@ void resize_axis_tables(int in_size, int out_size, int& ksize, std::vector<int>&
     if (xmax > in_size) xmax = in_size;
     xmax -= xmin;
     for (int x = 0; x < xmax; ++x) {
-      const double w = triangle((x + xmin - center + 0.5) * ss);
+      const double arg = (x + xmin - center + 0.5) * ss, w = cubic ? bicubic(arg) : triangle(arg);
       pre[x] = w;
       ww += w;
     }

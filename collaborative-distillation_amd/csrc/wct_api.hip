@@ -45,7 +45,7 @@ struct Module {
 
 // weight tables of one resize axis on the device (resize.hip)
 struct ResizeAxis {
-  int in_size = 0, out_size = 0, ksize = 0, first = 0, last = 0;   // [first, last): input rows / columns any output touches
+  int in_size = 0, out_size = 0, filter = 0, ksize = 0, first = 0, last = 0;   // [first, last): input rows / columns any output touches
   int* bounds = nullptr;          // [2 * out]            -- the three tables share ONE allocation (base = bounds)
   int* bounds_shifted = nullptr;  // the same with `first` subtracted from every start (the vertical pass reads a cropped image)
   int* kk = nullptr;              // [out * ksize]
@@ -95,8 +95,9 @@ struct wct_ctx {
   int cur_level = 0, cur_h = 0, cur_w = 0;  // content feature held in featC by wct_content_encode
   DevBuf u8c, u8s, u8o;   // fp32 planar staging of wct_stylize_u8 (content, style, result)
   DevBuf rsz_tmp;         // wct_resize_u8: uint8 image between the horizontal and the vertical pass
-  std::vector<ResizeAxis> rsz_axes;   // weight tables per (in, out) size, built on first use; least recently used evicted at 16
+  std::vector<ResizeAxis> rsz_axes;   // weight tables per (in, out, filter), built on first use; least recently used evicted at 16
   unsigned long long rsz_clock = 0;
+  DevBuf noise;       // wct_synthesize: the noise image (3 H W floats) the cascade reads as its content; kept until wct_destroy
   DevBuf l1img;       // level 1 fused: copy of the content image between wct_content_encode and wct_content_decode
   int cur_H = 0, cur_W = 0;
   int numpy_variant = 0;  // 1: `--numpy` semantics (util_wct.py:143): + I on the CONTENT covariance
@@ -1044,7 +1045,7 @@ void wct_destroy(wct_ctx* ctx) {
     if (ln->coop) (void)hipFree(ln->coop);
     ln->coop = nullptr;
   }
-  for (DevBuf* b : {&ctx->featC, &ctx->featS, &ctx->tmpT, &ctx->wsAsm, &ctx->small, &ctx->foldW, &ctx->foldW16, &ctx->eigC, &ctx->l1img, &ctx->u8c, &ctx->u8s, &ctx->u8o, &ctx->rsz_tmp}) release(*b);
+  for (DevBuf* b : {&ctx->featC, &ctx->featS, &ctx->tmpT, &ctx->wsAsm, &ctx->small, &ctx->foldW, &ctx->foldW16, &ctx->eigC, &ctx->l1img, &ctx->u8c, &ctx->u8s, &ctx->u8o, &ctx->rsz_tmp, &ctx->noise}) release(*b);
   for (ResizeAxis& a : ctx->rsz_axes) (void)hipFree(a.bounds);
   ctx->rsz_axes.clear();
   for (int l = 0; l < 6; ++l) {
@@ -1750,11 +1751,10 @@ int cascade(wct_ctx* ctx, const float* content, int H, int W, float alpha, int n
 }
 }  // namespace
 
-int wct_stylize(wct_ctx* ctx, const float* content, int H, int W, const float* style, int Hs, int Ws, float alpha,
-                int num_run, float* out, int* Ho, int* Wo) {
-  if (!ctx) return WCT_ERR_INVALID;
-  WCT_GUARD(ctx);
-  if (!content || !style || !out || num_run < 1) return fail(ctx, WCT_ERR_INVALID, "stylize: bad arguments");
+namespace {
+// the bodies of wct_stylize / wct_stylize_prepared behind their argument checks; wct_synthesize runs them on its noise image
+int stylize_impl(wct_ctx* ctx, const float* content, int H, int W, const float* style, int Hs, int Ws, float alpha, int num_run, float* out,
+                 int* Ho, int* Wo) {
   // style side of all five levels first, on the side lane: it only depends on the style image (the SAME image at
   // every level and every run, WCT.py:121-125), so it is computed once and overlaps the content cascade
   return with_deferred_solves(ctx, false, [&]() -> int {
@@ -1776,14 +1776,59 @@ int wct_stylize(wct_ctx* ctx, const float* content, int H, int W, const float* s
   });
 }
 
+int stylize_prepared_impl(wct_ctx* ctx, const char* what, const float* content, int H, int W, float alpha, int num_run, float* out, int* Ho, int* Wo) {
+  for (int level = 5; level >= 1; --level)
+    if (!ctx->eigS[level].p) return fail(ctx, WCT_ERR_STATE, "%s: no style statistics for level %d (wct_style_prepare / wct_style_import)", what, level);
+  return with_deferred_solves(ctx, false, [&]() -> int { return cascade(ctx, content, H, W, alpha, num_run, out, Ho, Wo); });
+}
+
+int noise_impl(wct_ctx* ctx, uint64_t seed, uint32_t stream_id, int H, int W, float* planar) {
+  ProfScope ps(ctx, ctx->main.stream, "noise_uniform<philox4x32-10>", 0, 12.0 * H * W);
+  HIPCHK(ctx, launch_noise_uniform(seed, stream_id, H, W, planar, ctx->main.stream));
+  return WCT_OK;
+}
+}  // namespace
+
+int wct_stylize(wct_ctx* ctx, const float* content, int H, int W, const float* style, int Hs, int Ws, float alpha,
+                int num_run, float* out, int* Ho, int* Wo) {
+  if (!ctx) return WCT_ERR_INVALID;
+  WCT_GUARD(ctx);
+  if (!content || !style || !out || num_run < 1) return fail(ctx, WCT_ERR_INVALID, "stylize: bad arguments");
+  return stylize_impl(ctx, content, H, W, style, Hs, Ws, alpha, num_run, out, Ho, Wo);
+}
+
 int wct_stylize_prepared(wct_ctx* ctx, const float* content, int H, int W, float alpha, int num_run, float* out, int* Ho,
                          int* Wo) {
   if (!ctx) return WCT_ERR_INVALID;
   WCT_GUARD(ctx);
   if (!content || !out || num_run < 1) return fail(ctx, WCT_ERR_INVALID, "stylize_prepared: bad arguments");
-  for (int level = 5; level >= 1; --level)
-    if (!ctx->eigS[level].p) return fail(ctx, WCT_ERR_STATE, "stylize_prepared: no style statistics for level %d (wct_style_prepare / wct_style_import)", level);
-  return with_deferred_solves(ctx, false, [&]() -> int { return cascade(ctx, content, H, W, alpha, num_run, out, Ho, Wo); });
+  return stylize_prepared_impl(ctx, "stylize_prepared", content, H, W, alpha, num_run, out, Ho, Wo);
+}
+
+int wct_noise_uniform(wct_ctx* ctx, uint64_t seed, uint32_t stream_id, int H, int W, float* planar) {
+  if (!ctx) return WCT_ERR_INVALID;
+  WCT_GUARD(ctx);
+  if (!planar || H < 1 || W < 1) return fail(ctx, WCT_ERR_INVALID, "noise_uniform: bad arguments (%dx%d, planar %s)", H, W, planar ? "given" : "NULL");
+  return noise_impl(ctx, seed, stream_id, H, W, planar);
+}
+
+int wct_synthesize(wct_ctx* ctx, const float* texture, int Ht, int Wt, int H, int W, uint64_t seed, uint32_t stream_id, float alpha, int num_run,
+                   float* out, int* Ho, int* Wo) {
+  if (!ctx) return WCT_ERR_INVALID;
+  WCT_GUARD(ctx);
+  if (!out || num_run < 1) return fail(ctx, WCT_ERR_INVALID, "synthesize: bad arguments (out %s, num_run %d)", out ? "given" : "NULL", num_run);
+  // the cascade starts at level 5, whose reflect padding needs two samples at 1/16 scale (encode_impl): say so before anything is written
+  if (H < 32 || W < 32) return fail(ctx, WCT_ERR_INVALID, "synthesize: output %dx%d is too small for the five-level cascade (32x32 at least)", H, W);
+  if (texture && (Ht < 32 || Wt < 32))
+    return fail(ctx, WCT_ERR_INVALID, "synthesize: texture %dx%d is too small for the five-level cascade (32x32 at least)", Ht, Wt);
+  if (!texture)
+    for (int level = 5; level >= 1; --level)
+      if (!ctx->eigS[level].p) return fail(ctx, WCT_ERR_STATE, "synthesize: no style statistics for level %d (wct_style_prepare / wct_style_import)", level);
+  if (int rc = ensure(ctx, ctx->noise, (size_t)3 * H * W * sizeof(float))) return rc;
+  float* noise = reinterpret_cast<float*>(ctx->noise.p);
+  if (int rc = noise_impl(ctx, seed, stream_id, H, W, noise)) return rc;
+  if (texture) return stylize_impl(ctx, noise, H, W, texture, Ht, Wt, alpha, num_run, out, Ho, Wo);
+  return stylize_prepared_impl(ctx, "synthesize", noise, H, W, alpha, num_run, out, Ho, Wo);
 }
 
 int wct_u8_to_planar(wct_ctx* ctx, const uint8_t* hwc, int H, int W, float* planar) {
@@ -1837,9 +1882,9 @@ int wct_resize_shape(int H, int W, int size, int* oH, int* oW) {
 }
 
 namespace {
-int resize_axis(wct_ctx* ctx, int in_size, int out_size, const ResizeAxis** out) {
+int resize_axis(wct_ctx* ctx, int in_size, int out_size, int filter, const ResizeAxis** out) {
   for (ResizeAxis& a : ctx->rsz_axes)
-    if (a.in_size == in_size && a.out_size == out_size) { a.used = ++ctx->rsz_clock; *out = &a; return WCT_OK; }
+    if (a.in_size == in_size && a.out_size == out_size && a.filter == filter) { a.used = ++ctx->rsz_clock; *out = &a; return WCT_OK; }
   if (ctx->rsz_axes.size() >= 16) {   // a bounded cache: evict the least recently used entry (hipFree waits for kernels still reading it)
     size_t lru = 0;
     for (size_t i = 1; i < ctx->rsz_axes.size(); ++i)
@@ -1849,8 +1894,8 @@ int resize_axis(wct_ctx* ctx, int in_size, int out_size, const ResizeAxis** out)
   }
   std::vector<int> bounds, kk;
   ResizeAxis a;
-  a.in_size = in_size; a.out_size = out_size;
-  resize_axis_tables(in_size, out_size, a.ksize, bounds, kk);
+  a.in_size = in_size; a.out_size = out_size; a.filter = filter;
+  resize_axis_tables(in_size, out_size, filter, a.ksize, bounds, kk);
   a.first = bounds[0];
   a.last = bounds[2 * (size_t)(out_size - 1)] + bounds[2 * (size_t)(out_size - 1) + 1];
   // bounds | shifted bounds | kk in ONE allocation and ONE copy: nothing to leak when a call fails part-way
@@ -1872,20 +1917,20 @@ int resize_axis(wct_ctx* ctx, int in_size, int out_size, const ResizeAxis** out)
   return WCT_OK;
 }
 
-int resize_impl(wct_ctx* ctx, const uint8_t* src, int H, int W, int oH, int oW, uint8_t* dst, float* planar) {
+int resize_impl(wct_ctx* ctx, const uint8_t* src, int H, int W, int oH, int oW, uint8_t* dst, float* planar, int filter = RESIZE_BILINEAR) {
   if (!src || (!dst && !planar) || H < 1 || W < 1 || oH < 1 || oW < 1 || H > 65535 || oH > 65535)
     return fail(ctx, WCT_ERR_INVALID, "resize_u8: bad arguments (%dx%d -> %dx%d)", H, W, oH, oW);
   const ResizeAxis *ax = nullptr, *ay = nullptr;
   // the vector may reallocate (or evict) when the second axis is added: look the first one up again afterwards
-  if (int rc = resize_axis(ctx, W, oW, &ax)) return rc;
-  if (int rc = resize_axis(ctx, H, oH, &ay)) return rc;
-  if (int rc = resize_axis(ctx, W, oW, &ax)) return rc;
-  if (int rc = resize_axis(ctx, H, oH, &ay)) return rc;
+  if (int rc = resize_axis(ctx, W, oW, filter, &ax)) return rc;
+  if (int rc = resize_axis(ctx, H, oH, filter, &ay)) return rc;
+  if (int rc = resize_axis(ctx, W, oW, filter, &ax)) return rc;
+  if (int rc = resize_axis(ctx, H, oH, filter, &ay)) return rc;
   const bool need_h = oW != W, need_v = oH != H;
   const int row0 = need_v ? ay->first : 0, rows = need_v ? ay->last - ay->first : H;
   if (need_h && (need_v || planar))
     if (int rc = ensure(ctx, ctx->rsz_tmp, (size_t)rows * oW * 3)) return rc;
-  ProfScope ps(ctx, ctx->main.stream, "resize_u8", 0, 3.0 * H * W + 3.0 * oH * oW * (planar ? 4 : 1));
+  ProfScope ps(ctx, ctx->main.stream, filter == RESIZE_BICUBIC ? "resize_u8<bicubic>" : "resize_u8", 0, 3.0 * H * W + 3.0 * oH * oW * (planar ? 4 : 1));
   HIPCHK(ctx, launch_resize_u8(src, H, W, oH, oW, ax->bounds, ax->kk, ax->ksize, ay->bounds_shifted, ay->kk, ay->ksize, row0, rows,
                                reinterpret_cast<uint8_t*>(ctx->rsz_tmp.p), dst, planar, ctx->main.stream));
   return WCT_OK;
@@ -1904,6 +1949,15 @@ int wct_resize_u8_to_planar(wct_ctx* ctx, const uint8_t* src_hwc, int H, int W, 
   WCT_GUARD(ctx);
   if (!planar) return fail(ctx, WCT_ERR_INVALID, "resize_u8_to_planar: bad arguments");
   return resize_impl(ctx, src_hwc, H, W, oH, oW, nullptr, planar);
+}
+
+int wct_resize_u8_filter(wct_ctx* ctx, const uint8_t* src_hwc, int H, int W, uint8_t* dst_hwc, float* planar, int oH, int oW, int filter) {
+  if (!ctx) return WCT_ERR_INVALID;
+  WCT_GUARD(ctx);
+  if ((dst_hwc == nullptr) == (planar == nullptr)) return fail(ctx, WCT_ERR_INVALID, "resize_u8_filter: exactly one of dst_hwc / planar must be given");
+  if (filter != WCT_FILTER_BILINEAR && filter != WCT_FILTER_BICUBIC)
+    return fail(ctx, WCT_ERR_INVALID, "resize_u8_filter: unknown filter %d (WCT_FILTER_BILINEAR = 0, WCT_FILTER_BICUBIC = 1)", filter);
+  return resize_impl(ctx, src_hwc, H, W, oH, oW, dst_hwc, planar, filter);
 }
 
 size_t wct_workspace_bytes(const wct_ctx* ctx, int H, int W, int Hs, int Ws) {

@@ -121,10 +121,13 @@ hipError_t launch_split_pack_phase(const float* wpk32, int cin, const unsigned* 
 // ---- image edge: uint8 HWC <-> planar fp32 (ToTensor / save_image of the reference's harness)
 hipError_t launch_u8_to_planar(const uint8_t* hwc, long npix, float* planar, hipStream_t s);
 hipError_t launch_planar_to_u8(const float* planar, long npix, uint8_t* hwc, int round_mode, hipStream_t s);
+// ---- seeded uniform noise (noise.hip): planar 3 x H x W fp32 in [0, 1), Philox4x32-10 keyed by seed, values defined by position alone
+hipError_t launch_noise_uniform(unsigned long long seed, unsigned stream_id, int H, int W, float* planar, hipStream_t s);
 // *dst = (double)*counter on the stream (wct_range_flag_f64: the saturation counter as a value a sharded run can all-reduce)
 hipError_t launch_counter_to_f64(const unsigned* counter, double* dst, hipStream_t s);
 // ---- image edge: transforms.Resize = Pillow's bilinear resampler, bit-exact (resize.hip)
-void resize_axis_tables(int in_size, int out_size, int& ksize, std::vector<int>& bounds, std::vector<int>& kk);   // host
+enum ResizeFilter : int { RESIZE_BILINEAR = 0, RESIZE_BICUBIC = 1 };   // = WCT_FILTER_* of include/wct_hip.h
+void resize_axis_tables(int in_size, int out_size, int filter, int& ksize, std::vector<int>& bounds, std::vector<int>& kk);   // host
 hipError_t launch_resize_u8(const uint8_t* in, int H, int W, int oH, int oW, const int* bounds_h, const int* kk_h, int ksize_h,
                             const int* bounds_v_shifted, const int* kk_v, int ksize_v, int row0, int rows, uint8_t* tmp, uint8_t* out,
                             float* planar, hipStream_t s);

@@ -7,6 +7,8 @@ What the reference script does around the hot path and where it lives here:
   WCT.py:37-75      checkpoint paths per --mode        -> checkpoint_args()
   data_loader.py:22-36   content x style pairs filtered by --picked_*_mark, listdir order   -> list_pairs()
   data_loader.py:50-59   PIL decode (.convert('RGB')), optional Resize, ToTensor            -> load_rgb_u8() + wct_resize_u8_to_planar / wct_u8_to_planar (GPU)
+  data_loader.py:61-76   --synthesis: textures of --texturePath, resized to --style_size, noise as content  -> texture_jobs() + synthesis_shape() +
+                         wct_resize_u8_filter (bicubic, GPU) + wct_synthesize (noise made on the GPU)
   WCT.py:120-125    the 5-level cascade, --num_run times -> wct_stylize (one C call)
   WCT.py:127-128    output name and save_image          -> out_name() + wct_planar_to_u8 (GPU) + PIL save
 A frame crosses PCIe as uint8 (3 B/px each way).  The reference's loop is strictly serial -- decode, .cuda(), cascade, save_image
@@ -14,7 +16,14 @@ A frame crosses PCIe as uint8 (3 B/px each way).  The reference's loop is strict
 `--pipeline N` (default 3; 0 = the serial loop) keeps N pairs in flight: a decode-ahead pool (PIL decode + copy into pinned memory, GIL
 released), asynchronous H2D / D2H around the GPU work of the SAME single engine in the SAME order, and a writer pool for Image.save.
 Output files are byte-identical to the serial loop's (tests/test_cli.py).  --numpy selects the reference's whiten_and_color_np semantics (+ I on the
-content covariance); --synthesis is rejected (broken in the reference: data_loader.py:74 calls torch.rand_like on a PIL image).
+content covariance).  --synthesis does what the reference's branch intends (it cannot run there: data_loader.py:74 calls
+torch.rand_like on a PIL image): every image of --texturePath, resized so that its long side is --style_size (Pillow's default
+filter at the reference's pin, bicubic), is the style of a cascade whose content is uniform noise -- seeded (--seed, the texture's
+index in the listing as the stream id: Philox4x32-10, include/wct_hip.h) and made on the GPU at the texture's size or
+--synthesis_size WxH; the result is saved as <log_mark>_mode=<m>_alpha=<a>_<texture stem>.jpg.  At the texture's size the result
+is the cascade's, as in the reference: every edge a multiple of 16 (floor pooling, four times).  --synthesis_size is the size of the
+FILE: the noise is made at the next multiples of 16 and the result cropped (top left) to WxH.  Only the decoded texture goes to the
+GPU and only the uint8 result comes back.
 Decoding/encoding files needs Pillow on the host (the reference's own dependency); the GPU library is mandatory: there
 is no CPU fallback.
 """
@@ -69,6 +78,11 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--weightPath", type=str, default=None,
                    help="folder of weight maps: content X.* uses DIR/X_0.png .. DIR/X_{K-1}.png (mode L, weight = value / 255, "
                         "summing to <= 1 at every pixel; the rest stays unstyled)")
+    # not in the reference: the noise of --synthesis (wct_noise_uniform) and the size of its output
+    p.add_argument("--seed", type=int, default=0, help="seed of the noise image of --synthesis (0 .. 2^64 - 1); the texture's index is the stream id")
+    p.add_argument("--synthesis_size", type=str, default=None,
+                   help="WxH of the images --synthesis writes, exactly (default: noise of the texture's size after --style_size, as in the "
+                        "reference, whose cascade floors every edge to a multiple of 16)")
     return p
 
 
@@ -331,6 +345,106 @@ def run_interp(args, wct, content_dir, logprinter) -> Tuple[float, int]:
     return avg, len(jobs)
 
 
+def synthesis_shape(H: int, W: int, size: int) -> Tuple[int, int]:
+    """(H, W) of a texture after the resize of data_loader.py:64-72: the LONGER edge becomes `size` (the second branch when they are
+    equal), the other int(short * size / long) -- Python's float division, then truncation; applied even when the long edge already
+    equals `size`; size 0 = no resize.  An edge that comes out as 0 is an error."""
+    if not size:
+        return H, W
+    if W > H:
+        neww = size
+        newh = int(H * neww / W)
+    else:
+        newh = size
+        neww = int(W * newh / H)
+    if newh < 1 or neww < 1:
+        raise ValueError("--style_size %d turns a %dx%d (WxH) texture into %dx%d" % (size, W, H, neww, newh))
+    return newh, neww
+
+
+def texture_jobs(texture_dir: str) -> List[str]:
+    """data_loader.py:28: the images of --texturePath in os.listdir order (no --picked_* filter)."""
+    return [x for x in os.listdir(texture_dir) if is_image_file(x)]
+
+
+def synthesis_out_name(args, texture_file: str) -> str:
+    """data_loader.py:76 + WCT.py:127: <log_mark>_mode=<m>_alpha=<a>_<texture stem>.jpg (stem = text before the FIRST dot)."""
+    return out_name(args, texture_file.split(".")[0] + ".jpg")
+
+
+def synthesis_size(text: str) -> Tuple[int, int]:
+    """--synthesis_size 'WxH' -> (H, W)."""
+    parts = text.lower().split("x")
+    try:
+        w, h = (int(v) for v in parts)
+    except ValueError:
+        raise ValueError("--synthesis_size: WxH expected (e.g. 3840x2160), got %r" % text) from None
+    if w < 1 or h < 1:
+        raise ValueError("--synthesis_size: positive WxH expected, got %r" % text)
+    return h, w
+
+
+def synthesis_noise_shape(H: int, W: int) -> Tuple[int, int]:
+    """The noise size behind a --synthesis_size H x W file: the cascade returns 16 floor(edge / 16) (floor pooling at every level), so
+    the noise takes the next multiples of 16 and the result is cropped to H x W."""
+    return (H + 15) // 16 * 16, (W + 15) // 16 * 16
+
+
+def check_synthesis_args(args) -> None:
+    if not args.synthesis:
+        if args.seed != 0:
+            raise ValueError("--seed needs --synthesis")
+        if args.synthesis_size is not None:
+            raise ValueError("--synthesis_size needs --synthesis")
+        return
+    for flag, name in ((args.maskPath, "--maskPath"), (args.interp_styles, "--interp_styles"), (args.weightPath, "--weightPath")):
+        if flag is not None:
+            raise ValueError("--synthesis does not mix with %s" % name)
+    if not 0 <= args.seed < 1 << 64:
+        raise ValueError("--seed: 0 .. 2^64 - 1 expected, got %d" % args.seed)
+    if args.synthesis_size is not None:
+        synthesis_size(args.synthesis_size)
+
+
+def run_synthesis(args, wct, logprinter) -> Tuple[float, int]:
+    """--synthesis: one image per texture of --texturePath (wct_synthesize: noise of --seed and stream id = the texture's index as the
+    content, the texture as the style); the serial loop.  Returns (total seconds, textures)."""
+    import torch
+    from PIL import Image
+    jobs = texture_jobs(args.texturePath)
+    logprinter("Number of content-style pairs: %s" % len(jobs))
+    size = synthesis_size(args.synthesis_size) if args.synthesis_size is not None else None
+    avg = 0.0
+    for i, tfile in enumerate(jobs):
+        imname = tfile.split(".")[0] + ".jpg"
+        logprinter("\n" + "*" * 30 + ' #%s: Transferring "%s"' % (i, imname))
+        t_u8 = torch.from_numpy(load_rgb_u8(os.path.join(args.texturePath, tfile))).pin_memory().cuda(non_blocking=True)
+        t0 = time.time()
+        if args.style_size:
+            t_f32 = wct.resize_u8(t_u8, synthesis_shape(int(t_u8.shape[0]), int(t_u8.shape[1]), args.style_size), to_tensor=True, filter="bicubic")
+        else:
+            t_f32 = wct.to_tensor_u8(t_u8)
+        if size is not None:
+            H, W = synthesis_noise_shape(*size)
+        else:
+            H, W = int(t_f32.shape[2]), int(t_f32.shape[3])
+        res = wct.synthesize(t_f32, H, W, seed=args.seed, stream_id=i, alpha=args.alpha, num_run=args.num_run)
+        if wct.saturation_count(reset=True):
+            logprinter("WARNING: f16x3 range exceeded for this texture -> recomputing it with exact-fp32 convolutions")
+            wct.set_conv_mode("fp32")
+            res = wct.synthesize(t_f32, H, W, seed=args.seed, stream_id=i, alpha=args.alpha, num_run=args.num_run)
+            wct.sync()
+            wct.set_conv_mode("f16x3")
+        if size is not None:
+            res = res[:, :, :size[0], :size[1]]
+        out = wct.to_u8(res, args.round_mode).cpu().numpy()
+        Image.fromarray(out).save(synthesis_out_name(args, tfile))
+        dt = time.time() - t0
+        avg += dt
+        logprinter("Elapsed time is: %.4f seconds" % dt)
+    return avg, len(jobs)
+
+
 class LogPrinter:     # WCT.py:78-82
     def __init__(self, debug: bool, path: str):
         self.log = sys.stdout if debug else open(path, "a+")
@@ -536,13 +650,21 @@ def main(argv: Optional[List[str]] = None) -> int:
     checkpoint_args(args)
     check_region_args(args)
     check_interp_args(args)
-    if args.synthesis:
-        raise NotImplementedError("--synthesis is broken in the reference (data_loader.py:74) and not part of this path")
+    check_synthesis_args(args)
     os.makedirs(args.outf, exist_ok=True)
     logprinter = LogPrinter(args.debug, os.path.join(args.outf, "log_%s_%s.txt" % (args.log_mark, args.mode)))
     logprinter(sorted(vars(args).items()))
     content_dir = args.UHD_contentPath if args.UHD else args.contentPath
     style_dir = args.UHD_stylePath if args.UHD else args.stylePath
+    if args.synthesis:
+        from .wct import WCT
+        wct = WCT(args)
+        if args.pipeline > 0:
+            logprinter("--pipeline is ignored with --synthesis: texture synthesis uses the serial loop")
+        avg, n = run_synthesis(args, wct, logprinter)
+        if n:
+            logprinter("Processed %d images. Average processing time per pair is: %.4f seconds" % (n, avg / n))
+        return 0
     if args.maskPath is not None:
         jobs = region_jobs(content_dir, args.maskPath, args.picked_content_mark)
         from .wct import WCT

@@ -27,6 +27,7 @@ SYMBOLS = [
     "wct_style_prepare_levels", "wct_style_stats_count", "wct_style_export", "wct_style_import", "wct_stylize_prepared",
     "wct_u8_to_planar", "wct_planar_to_u8", "wct_stylize_u8", "wct_resize_shape", "wct_resize_u8", "wct_resize_u8_to_planar",
     "wct_moments_labeled", "wct_apply_labeled", "wct_stylize_regions",
+    "wct_noise_uniform", "wct_synthesize", "wct_resize_u8_filter",
     "wct_stylize_interp", "wct_style_blend", "wct_stylize_blend", "wct_moments_weighted", "wct_apply_mixed",
     "wct_workspace_bytes", "wct_reserve", "wct_set_conv_mode", "wct_set_numpy_variant", "wct_set_overlap", "wct_profile_enable", "wct_profile_reset", "wct_profile_read",
 ]
@@ -60,6 +61,7 @@ HALO_MODES = {"auto": 0, "recompute": 1, "exchange": 2}
 STYLE_MODES = {"auto": 0, "owner": 1, "strips": 2, "replicate": 3}
 SHARD_BROADCAST_MAP = 1
 SHARD_FAST_FOLD = 2
+RESIZE_FILTERS = {"bilinear": 0, "bicubic": 1}      # WCT_FILTER_*
 
 
 class WctError(RuntimeError):
@@ -147,6 +149,9 @@ def load() -> ctypes.CDLL:
     lib.wct_resize_shape.argtypes = [c_int, c_int, c_int, ip, ip]
     lib.wct_resize_u8.argtypes = [c_void_p, vp, c_int, c_int, vp, c_int, c_int]
     lib.wct_resize_u8_to_planar.argtypes = [c_void_p, vp, c_int, c_int, vp, c_int, c_int]
+    lib.wct_resize_u8_filter.argtypes = [c_void_p, vp, c_int, c_int, vp, vp, c_int, c_int, c_int]
+    lib.wct_noise_uniform.argtypes = [c_void_p, ctypes.c_uint64, ctypes.c_uint32, c_int, c_int, vp]
+    lib.wct_synthesize.argtypes = [c_void_p, vp, c_int, c_int, c_int, c_int, ctypes.c_uint64, ctypes.c_uint32, c_float, c_int, vp, ip, ip]
     lib.wct_workspace_bytes.argtypes = [c_void_p, c_int, c_int, c_int, c_int]
     lib.wct_workspace_bytes.restype = c_size_t
     lib.wct_reserve.argtypes = [c_void_p, c_int, c_int, c_int, c_int]

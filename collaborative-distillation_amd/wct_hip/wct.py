@@ -421,15 +421,25 @@ class WCT:
         return oh.value, ow.value
 
     @torch.no_grad()
-    def resize_u8(self, img_u8: torch.Tensor, size, to_tensor: bool = False) -> torch.Tensor:
+    def resize_u8(self, img_u8: torch.Tensor, size, to_tensor: bool = False, filter: str = "bilinear") -> torch.Tensor:
         """transforms.Resize(size) of data_loader.py:52-56 on the GPU, bit-exact with Pillow's bilinear Image.resize: `size` is an
         int (smaller edge, torchvision's rule) or an (oH, oW) pair.  to_tensor=True returns ToTensor()'s fp32 1x3xoHxoW instead of
-        uint8 HWC (one pass less)."""
+        uint8 HWC (one pass less).  filter="bicubic" is Pillow's Image.BICUBIC -- what the reference's texture resize
+        (data_loader.py:72: Image.resize without a filter argument, at its Pillow pin) uses; it takes an explicit (oH, oW)."""
+        if filter not in _lib.RESIZE_FILTERS:
+            raise ValueError("filter must be 'bilinear' or 'bicubic', got %r" % (filter,))
+        if filter != "bilinear" and isinstance(size, int):
+            raise ValueError("resize_u8: filter=%r takes an explicit (oH, oW); torchvision's smaller-edge rule belongs to the bilinear Resize" % filter)
         x = self._u8(img_u8)
         H, W = int(x.shape[0]), int(x.shape[1])
         oH, oW = self.resize_shape(H, W, size) if isinstance(size, int) else (int(size[0]), int(size[1]))
         self._stream()
-        if to_tensor:
+        if filter != "bilinear":
+            out = torch.empty((1, 3, oH, oW), device=x.device, dtype=torch.float32) if to_tensor else \
+                torch.empty((oH, oW, 3), device=x.device, dtype=torch.uint8)
+            self._chk(self._lib.wct_resize_u8_filter(self._ctx, x.data_ptr(), H, W, None if to_tensor else out.data_ptr(),
+                                                     out.data_ptr() if to_tensor else None, oH, oW, _lib.RESIZE_FILTERS[filter]))
+        elif to_tensor:
             out = torch.empty((1, 3, oH, oW), device=x.device, dtype=torch.float32)
             self._chk(self._lib.wct_resize_u8_to_planar(self._ctx, x.data_ptr(), H, W, out.data_ptr(), oH, oW))
         else:
@@ -656,6 +666,55 @@ class WCT:
         self._stream()
         self._chk(self._lib.wct_stylize(self._ctx, c.data_ptr(), H, W, s.data_ptr(), Hs, Ws, alpha, int(num_run),
                                         out.data_ptr(), byref(ho), byref(wo)))
+        return out.view(-1)[: 3 * ho.value * wo.value].view(1, 3, ho.value, wo.value)
+
+    # ------------------------------------------------------------------ texture synthesis
+    @torch.no_grad()
+    def noise(self, H: int, W: int, seed: int = 0, stream_id: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Uniform noise in [0, 1) as a [1, 3, H, W] fp32 image made on the GPU (wct_noise_uniform): Philox4x32-10 keyed by the 64-bit
+        `seed`, values defined by (seed, stream_id, position) alone -- include/wct_hip.h states the mapping; torch's generator is not
+        involved.  `out`: an fp32 tensor on this device with 3*H*W values, contiguous, any 4-byte alignment (a view is fine)."""
+        H, W, seed, stream_id = int(H), int(W), int(seed), int(stream_id)
+        if not (0 <= seed < 1 << 64) or not (0 <= stream_id < 1 << 32):
+            raise ValueError("noise: seed must fit 64 bits and stream_id 32 bits (unsigned), got %d, %d" % (seed, stream_id))
+        if H < 1 or W < 1:
+            raise ValueError("noise: H, W >= 1 expected, got %d x %d" % (H, W))
+        if out is None:
+            out = torch.empty((1, 3, H, W), device=self.stats_device, dtype=torch.float32)
+        elif out.dtype != torch.float32 or not out.is_cuda or out.device.index != self.device or not out.is_contiguous() \
+                or out.numel() != 3 * H * W:
+            raise ValueError("out must be a contiguous fp32 tensor on cuda:%d with %d values" % (self.device, 3 * H * W))
+        self._stream()
+        self._chk(self._lib.wct_noise_uniform(self._ctx, seed, stream_id, H, W, out.data_ptr()))
+        return out.view(1, 3, H, W)
+
+    @torch.no_grad()
+    def synthesize(self, texture: Optional[torch.Tensor], H: Optional[int] = None, W: Optional[int] = None, seed: int = 0,
+                   stream_id: int = 0, alpha: Optional[float] = None, num_run: int = 1, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Texture synthesis (`--synthesis`, data_loader.py:61-76): the cascade with noise(H, W, seed, stream_id) as the content and
+        `texture` as the style, in one library call (wct_synthesize) -- bit-identical to stylize(noise(...), texture, ...), with the
+        noise kept inside the context.  The default size is the texture's.  texture=None runs against the style statistics already in
+        the context (style_prepare / style_import / style_blend), H and W are then required.  Texture interpolation needs no entry of
+        its own: stylize_interp(wct.noise(H, W, seed), textures, weights) composes."""
+        alpha = self.alpha if alpha is None else float(alpha)
+        seed, stream_id = int(seed), int(stream_id)
+        if not (0 <= seed < 1 << 64) or not (0 <= stream_id < 1 << 32):
+            raise ValueError("synthesize: seed must fit 64 bits and stream_id 32 bits (unsigned), got %d, %d" % (seed, stream_id))
+        t = None
+        Ht = Wt = 0
+        if texture is not None:
+            t = self._img(texture)
+            Ht, Wt = int(t.shape[1]), int(t.shape[2])
+        elif H is None or W is None:
+            raise ValueError("synthesize: texture=None (prepared statistics) needs H and W")
+        H = Ht if H is None else int(H)
+        W = Wt if W is None else int(W)
+        out = self._out_image(out, max(H, 0), max(W, 0))
+        ho, wo = c_int(), c_int()
+        self._stream()
+        self._chk(self._lib.wct_synthesize(self._ctx, t.data_ptr() if t is not None else None, Ht, Wt, H, W, seed, stream_id, alpha,
+                                           int(num_run), out.data_ptr(), byref(ho), byref(wo)))
+        self._style_keep = t      # the side stream reads it asynchronously
         return out.view(-1)[: 3 * ho.value * wo.value].view(1, 3, ho.value, wo.value)
 
     # ------------------------------------------------------------------ spatial control (regions)

@@ -372,6 +372,37 @@ int wct_style_import(wct_ctx* ctx, int level, const double* stats);
 int wct_stylize_prepared(wct_ctx* ctx, const float* content, int H, int W, float alpha, int num_run, float* out, int* Ho,
                          int* Wo);
 
+/* Texture synthesis, the WCT paper's fourth application: `--synthesis` of the reference (WCT.py:26, PytorchWCT/data_loader.py:61-76) --
+ * the cascade of WCT.py:120-125 with uniform noise as the content and the texture as the style.  The reference's own branch cannot
+ * run (data_loader.py:74 calls torch.rand_like on a PIL image); its intent is what these entries do, with the noise made on the
+ * device: an image-sized fp32 buffer never crosses the host interface.
+ *   wct_noise_uniform  fills planar (3 x H x W fp32, device) with uniform noise in [0, 1 - 2^-24].  The values are DEFINED BY POSITION,
+ *                      never by launch geometry, library version or any framework's generator, so that any host can reproduce them:
+ *                        generator  Philox4x32-10 (Salmon et al., SC'11 / Random123): multipliers 0xD2511F53, 0xCD9E8D57, key
+ *                                   increments 0x9E3779B9, 0xBB67AE85, 10 rounds
+ *                        key        (seed & 0xffffffff, seed >> 32)
+ *                        counter    (i & 0xffffffff, i >> 32, stream_id, 0) for block i = e >> 2 of the flat element index
+ *                                   e = c H W + y W + x;  element e takes output word e & 3 of its block
+ *                        value      float(word >> 8) * 2^-24 (exact in fp32; the range of torch.rand)
+ *                      stream_id separates independent images of one seed (the command line uses the texture's index).  planar may
+ *                      have any 4-byte alignment (16-byte stores are used where it is 16-byte aligned).  H, W >= 1.  Runs on the
+ *                      context's stream; allocates nothing; does not synchronise.
+ *   wct_synthesize     = wct_noise_uniform(seed, stream_id, H, W) into a buffer of the context, then wct_stylize(noise, texture, ...):
+ *                      bit-identical to those two calls.  texture: planar 3 x Ht x Wt, or NULL = wct_stylize_prepared against the style
+ *                      statistics already in the context (wct_style_prepare / wct_style_import / wct_style_blend: one texture, many
+ *                      seeds or sizes; blended textures).  The output size H x W is independent of the texture's (both at least 32 x 32:
+ *                      level 5 works at 1/16 scale); out must hold 3*H*W floats, Ho x Wo = 16 floor(H / 16) x 16 floor(W / 16).  Like
+ *                      wct_stylize on the 16x path the call never synchronises, allocates nothing after the first call of a size and can
+ *                      be captured into one HIP graph -- seed and stream_id are then kernel arguments BAKED into the graph: a replay
+ *                      repeats the same noise; capture one graph per seed, or update the node's arguments.  The f16x3 range flag
+ *                      behaves as in wct_stylize.  Bad arguments return WCT_ERR_INVALID before anything is written.
+ * The noise buffer (3*H*W floats) belongs to the context: allocated on the first wct_synthesize of a size, kept until wct_destroy.  It
+ * comes ON TOP of wct_workspace_bytes(H, W, Ht, Wt), and wct_reserve does not allocate it.
+ * Texture interpolation needs no entry of its own: wct_noise_uniform into a caller buffer + wct_stylize_interp. */
+int wct_noise_uniform(wct_ctx* ctx, uint64_t seed, uint32_t stream_id, int H, int W, float* planar);
+int wct_synthesize(wct_ctx* ctx, const float* texture, int Ht, int Wt, int H, int W, uint64_t seed, uint32_t stream_id, float alpha,
+                   int num_run, float* out, int* Ho, int* Wo);
+
 /* Image edge: the reference harness's ToTensor (PytorchWCT/data_loader.py:57-58: uint8 HWC -> fp32 CHW
  * / 255) and save_image (WCT.py:128; torchvision 0.2.1: mul(255).clamp(0,255).byte()) on the device.  Pointers are
  * device pointers, uint8 images are H x W x 3 interleaved and 4-byte aligned.  round_mode 0 = truncation (the
@@ -388,14 +419,23 @@ int wct_stylize_u8(wct_ctx* ctx, const uint8_t* content_hwc, int H, int W, const
  *   wct_resize_shape         torchvision's size rule: the smaller edge becomes `size` (0 or already equal: unchanged)
  *   wct_resize_u8            uint8 HWC -> uint8 HWC of oH x oW (any target size; equal sizes copy)
  *   wct_resize_u8_to_planar  the same followed by ToTensor (data_loader.py:57: planar fp32 / 255) without a uint8 round trip
+ *   wct_resize_u8_filter     the same resampler with the filter chosen by id: WCT_FILTER_BILINEAR (the two entries above, bit for
+ *                            bit) or WCT_FILTER_BICUBIC = Pillow's bicubic_filter (a = -0.5, support 2.0), what Image.resize((w, h))
+ *                            WITHOUT a filter argument uses at the reference's Pillow pin: the texture resize of --synthesis
+ *                            (data_loader.py:72).  Exactly one of dst_hwc (uint8 HWC) / planar (fp32 / 255, ToTensor) is non-NULL.
+ *                            Bit-exact with Pillow's Image.resize(..., Image.BICUBIC) (tests/test_synthesis_cpu.py, _gpu.py).
  * Pointers are device pointers (any alignment: the kernels read single bytes); H and oH <= 65535 (the row index is a grid
- * dimension).  Weight tables per (input, output) size are built on the host on first use (O(W + H)) and cached in the context
+ * dimension).  Weight tables per (input, output, filter) are built on the host on first use (O(W + H)) and cached in the context
  * (16 axes, least recently used evicted). */
+#define WCT_FILTER_BILINEAR 0
+#define WCT_FILTER_BICUBIC 1
 int wct_resize_shape(int H, int W, int size, int* oH, int* oW);
 int wct_resize_u8(wct_ctx* ctx, const uint8_t* src_hwc, int H, int W, uint8_t* dst_hwc, int oH, int oW);
 int wct_resize_u8_to_planar(wct_ctx* ctx, const uint8_t* src_hwc, int H, int W, float* planar, int oH, int oW);
+int wct_resize_u8_filter(wct_ctx* ctx, const uint8_t* src_hwc, int H, int W, uint8_t* dst_hwc, float* planar, int oH, int oW, int filter);
 
-/* bytes of internal workspace a wct_stylize of this size will hold; wct_reserve allocates it up front */
+/* bytes of internal workspace a wct_stylize of this size will hold; wct_reserve allocates it up front (wct_synthesize's noise buffer,
+ * 3*H*W floats, comes on top of both: see there) */
 size_t wct_workspace_bytes(const wct_ctx* ctx, int H, int W, int Hs, int Ws);
 int wct_reserve(wct_ctx* ctx, int H, int W, int Hs, int Ws);
 
