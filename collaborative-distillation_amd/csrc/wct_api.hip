@@ -81,6 +81,7 @@ struct wct_ctx {
   hipEvent_t ev_join = nullptr;   // side -> main (wct_style_moments: the style strip's sums are ready)
   hipEvent_t ev_smom[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // wct_stylize_sharded, strips: level L's style sums are ready (side -> main)
   hipEvent_t ev_sar[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};    // ... and level L's all-reduce has been issued (main -> side)
+  hipEvent_t ev_switch = nullptr;   // wct_set_stream: old caller stream -> new caller stream (the workspace is shared between them)
   hipEvent_t ev_fork = nullptr, ev_style[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   int eig_skip = 0, eig_calls = 0;
   int foldgemm = 1;   // 1: the wide models' folds as fp64 matrix-core GEMMs (debug key "foldgemm"; 0: misc.hip fold_block_kernel)
@@ -151,6 +152,32 @@ struct wct_ctx {
   // per wct_stylize_blend call (the regions' moments / maps / feature buffers are reused)
   DevBuf blendW, blendStat, wsBlendPool, wsBlendApply;
   void* blend_host = nullptr;
+  // debug hooks (wct_debug_set "poison", wct_debug_get "ws_allocs" / "ws_bytes")
+  int poison = -1;                     // 0..255: every ensure() allocation is filled with this byte; -1: off
+  unsigned long long ws_allocs = 0;    // ensure() allocations so far
+  bool pair_open = false;              // between wct_content_encode and wct_content_decode: featC / l1img are state
+
+  // EVERY DevBuf of the context, once, with its class: f(buf, owning lane, scratch).  Scratch = no later call is documented to read
+  // what an earlier call left there, so the "poison" hook may overwrite it between calls; state must survive (style slots, the
+  // style-side folds, and the content feature / image of an open wct_content_encode -> wct_content_decode pair).  wct_destroy
+  // releases through this list: a DevBuf added to the struct has to be classified here or it leaks.
+  template <typename F>
+  void each_buf(F&& f) {
+    for (Lane* ln : {&main, &side})
+      for (DevBuf* b : {&ln->actA, &ln->actB, &ln->wsMom, &ln->wsEig, &ln->sums}) f(*b, ln, true);
+    for (DevBuf* b : {&featS, &tmpT, &wsAsm, &small, &foldW, &foldW16, &eigC, &u8c, &u8s, &u8o, &rsz_tmp, &noise, &packed,
+                      &shIn, &shOut, &shNext, &shEdge, &shStyle, &shStats, &shMb,
+                      &regLab, &regHist, &regSums, &regMb, &regFeat, &wsRegMom, &wsRegApply,
+                      &blendW, &blendStat, &wsBlendPool, &wsBlendApply})
+      f(*b, &main, true);
+    for (DevBuf& b : eigCR) f(b, &main, true);       // the regions' content-side results: rewritten by every level that reads them
+    for (DevBuf* b : {&featC, &l1img}) f(*b, &main, !pair_open);
+    for (int l = 0; l < 6; ++l) {
+      f(eigS[l], &side, false);                      // prepared style statistics (wct_style_prepare / _import / _blend / wct_stylize_interp)
+      f(foldS[l], &side, false);                     // their style-side fold, valid while fold_ready[l]
+      for (int k = 0; k < 8; ++k) f(eigR[k][l], &side, false);   // the K style slots of the regions / blend / interpolation calls
+    }
+  }
 };
 
 // RCCL, resolved at run time (wct_comm_load): the library keeps no link-time dependency on it
@@ -228,6 +255,26 @@ int ensure(wct_ctx* ctx, DevBuf& b, size_t bytes) {
   const size_t want = (bytes + 255) & ~(size_t)255;
   HIPCHK(ctx, hipMalloc(&b.p, want));
   b.cap = want;
+  ++ctx->ws_allocs;
+  if (ctx->poison >= 0) {   // debug hook "poison": a fresh allocation is usually zero pages -- it must not escape the fill
+    HIPCHK(ctx, hipMemsetAsync(b.p, ctx->poison, want, ctx->main.stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->main.stream));   // whichever lane writes the buffer first finds the fill finished
+  }
+  return WCT_OK;
+}
+
+// debug hook "poison": fill every allocated SCRATCH buffer (wct_ctx::each_buf) with `byte`, each on the lane that owns it, between
+// two synchronisations of both lanes
+int poison_scratch(wct_ctx* ctx, int byte) {
+  HIPCHK(ctx, hipStreamSynchronize(ctx->main.stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->side.stream));
+  hipError_t e = hipSuccess;
+  ctx->each_buf([&](DevBuf& b, Lane* ln, bool scratch) {
+    if (scratch && b.p && e == hipSuccess) e = hipMemsetAsync(b.p, byte, b.cap, ln->stream);
+  });
+  HIPCHK(ctx, e);
+  HIPCHK(ctx, hipStreamSynchronize(ctx->main.stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->side.stream));
   return WCT_OK;
 }
 
@@ -1018,6 +1065,7 @@ int wct_create(int device, wct_ctx** out) {
     ok = ok && hipMalloc(reinterpret_cast<void**>(&ln->coop), 64) == hipSuccess && hipMemset(ln->coop, 0, 64) == hipSuccess;
   ok = ok && hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) == hipSuccess;
   ok = ok && hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) == hipSuccess;
+  ok = ok && hipEventCreateWithFlags(&c->ev_switch, hipEventDisableTiming) == hipSuccess;
   for (int l = 1; l <= 5 && ok; ++l)
     ok = hipEventCreateWithFlags(&c->ev_style[l], hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&c->ev_smom[l], hipEventDisableTiming) == hipSuccess &&
          hipEventCreateWithFlags(&c->ev_sar[l], hipEventDisableTiming) == hipSuccess;
@@ -1040,37 +1088,27 @@ void wct_destroy(wct_ctx* ctx) {
   prof_collect(ctx);
   for (int k = 0; k < 2; ++k)
     for (int l = 0; l < 6; ++l) free_module(ctx->mod[k][l]);
+  ctx->each_buf([](DevBuf& b, Lane*, bool) { release(b); });
   for (Lane* ln : {&ctx->main, &ctx->side}) {
-    for (DevBuf* b : {&ln->actA, &ln->actB, &ln->wsMom, &ln->wsEig, &ln->sums}) release(*b);
     if (ln->coop) (void)hipFree(ln->coop);
     ln->coop = nullptr;
   }
-  for (DevBuf* b : {&ctx->featC, &ctx->featS, &ctx->tmpT, &ctx->wsAsm, &ctx->small, &ctx->foldW, &ctx->foldW16, &ctx->eigC, &ctx->l1img, &ctx->u8c, &ctx->u8s, &ctx->u8o, &ctx->rsz_tmp, &ctx->noise}) release(*b);
   for (ResizeAxis& a : ctx->rsz_axes) (void)hipFree(a.bounds);
   ctx->rsz_axes.clear();
   for (int l = 0; l < 6; ++l) {
-    release(ctx->eigS[l]);
-    release(ctx->foldS[l]);
     if (ctx->ev_style[l]) (void)hipEventDestroy(ctx->ev_style[l]);
     if (ctx->ev_smom[l]) (void)hipEventDestroy(ctx->ev_smom[l]);
     if (ctx->ev_sar[l]) (void)hipEventDestroy(ctx->ev_sar[l]);
   }
   if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
   if (ctx->ev_join) (void)hipEventDestroy(ctx->ev_join);
-  for (DevBuf* b : {&ctx->shIn, &ctx->shOut, &ctx->shNext, &ctx->shEdge, &ctx->shStyle, &ctx->shStats, &ctx->shMb}) release(*b);
-  for (int k = 0; k < 8; ++k) {
-    for (int l = 0; l < 6; ++l) release(ctx->eigR[k][l]);
-    release(ctx->eigCR[k]);
-  }
-  for (DevBuf* b : {&ctx->regLab, &ctx->regHist, &ctx->regSums, &ctx->regMb, &ctx->regFeat, &ctx->wsRegMom, &ctx->wsRegApply}) release(*b);
+  if (ctx->ev_switch) (void)hipEventDestroy(ctx->ev_switch);
   if (ctx->reg_hist_host) (void)hipHostFree(ctx->reg_hist_host);
-  for (DevBuf* b : {&ctx->blendW, &ctx->blendStat, &ctx->wsBlendPool, &ctx->wsBlendApply}) release(*b);
   if (ctx->blend_host) (void)hipHostFree(ctx->blend_host);
 
   if (ctx->side.stream) (void)hipStreamDestroy(ctx->side.stream);
   if (ctx->sat_dev) (void)hipFree(ctx->sat_dev);
   if (ctx->comm && ctx->comm_owned && g_rccl.CommDestroy) (void)g_rccl.CommDestroy(ctx->comm);
-  release(ctx->packed);
   if (ctx->sat_host) (void)hipHostFree(ctx->sat_host);
   if (ctx->ok_log) (void)hipFree(ctx->ok_log);
   if (ctx->ok_host) (void)hipHostFree(ctx->ok_host);
@@ -1083,7 +1121,19 @@ const char* wct_last_error(const wct_ctx* ctx) { return ctx ? ctx->err.c_str() :
 int wct_set_stream(wct_ctx* ctx, void* s) {
   if (!ctx) return WCT_ERR_INVALID;
   WCT_GUARD(ctx);
-  ctx->main.stream = reinterpret_cast<hipStream_t>(s);
+  hipStream_t ns = reinterpret_cast<hipStream_t>(s);
+  if (ns == ctx->main.stream) return WCT_OK;
+  // Calls issued under two streams share every workspace of the context: the new stream waits for whatever the context has enqueued
+  // on the old one (the side lane orders itself: it is one stream, and forks from / joins the caller's stream by events).  The old
+  // stream must still exist; if it cannot take the event the switch goes ahead unordered, as it always did.
+  // A stream that is being captured into a graph takes no dependency on work outside the capture (the caller synchronised before it began).
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(ns, &cap) != hipSuccess) { (void)hipGetLastError(); cap = hipStreamCaptureStatusNone; }
+  if (cap == hipStreamCaptureStatusNone) {
+    if (ctx->ev_switch && hipEventRecord(ctx->ev_switch, ctx->main.stream) == hipSuccess) HIPCHK(ctx, hipStreamWaitEvent(ns, ctx->ev_switch, 0));
+    else (void)hipGetLastError();
+  }
+  ctx->main.stream = ns;
   return WCT_OK;
 }
 
@@ -1147,6 +1197,14 @@ int wct_debug_set(wct_ctx* ctx, const char* key, double value) {
   else if (!strcmp(key, "nscoop")) ctx->nscoop = (int)value;      // 0: multi-launch, 1: single launch, 2: single launch with an injected placement fault
   else if (!strcmp(key, "mom32")) ctx->mom32 = (int)value;       // 0 / 1 / 2, see wct_ctx
   else if (!strcmp(key, "in3wide")) ctx->in3wide = (int)value;   // 2 / 1 / 0, see wct_ctx
+  else if (!strcmp(key, "poison")) {
+    // -1: off; 0..255: fill every allocated scratch buffer with this byte NOW (both lanes synchronised) and every later ensure()
+    // allocation too, until turned off.  State survives (wct_ctx::each_buf).
+    if (value < 0) { ctx->poison = -1; return WCT_OK; }
+    if (value > 255 || value != (double)(int)value) return fail(ctx, WCT_ERR_INVALID, "debug_set: 'poison' takes a byte 0..255, or -1 for off");
+    ctx->poison = (int)value;
+    return poison_scratch(ctx, ctx->poison);
+  }
   else if (!strcmp(key, "eig_skip")) {
     // MEASUREMENT ONLY: solves are left out and stale results reused -- wrong pictures by design; refused outside a debug run
     if (!getenv("WCT_DEBUG")) return fail(ctx, WCT_ERR_INVALID, "debug_set: 'eig_skip' produces wrong results by design (timing experiment); set WCT_DEBUG to allow it");
@@ -1176,7 +1234,7 @@ int wct_debug_set(wct_ctx* ctx, const char* key, double value) {
     ctx->side.stream = ns;
     return WCT_OK;
   }
-  else return fail(ctx, WCT_ERR_INVALID, "debug_set: unknown key '%s' (fuse, sp, l1fuse, u8fuse, upconv, fastfold, interleave, foldgemm, nscoop, in3wide, mom32, eig_skip, side_priority)", key);
+  else return fail(ctx, WCT_ERR_INVALID, "debug_set: unknown key '%s' (fuse, sp, l1fuse, u8fuse, upconv, fastfold, interleave, foldgemm, nscoop, in3wide, mom32, eig_skip, side_priority, poison)", key);
   HIPCHK(ctx, hipStreamSynchronize(ctx->side.stream));
   return WCT_OK;
 }
@@ -1195,7 +1253,14 @@ int wct_debug_get(wct_ctx* ctx, const char* key, double* value) {
     *value = (double)n[0] + (double)n[1];
     return WCT_OK;
   }
-  return fail(ctx, WCT_ERR_INVALID, "debug_get: unknown key '%s' (nscoop_aborts, nscoop_solves, nscoop_off)", key);
+  if (!strcmp(key, "ws_allocs")) { *value = (double)ctx->ws_allocs; return WCT_OK; }
+  if (!strcmp(key, "ws_bytes")) {
+    size_t total = 0;
+    ctx->each_buf([&](DevBuf& b, Lane*, bool) { total += b.cap; });
+    *value = (double)total;
+    return WCT_OK;
+  }
+  return fail(ctx, WCT_ERR_INVALID, "debug_get: unknown key '%s' (nscoop_aborts, nscoop_solves, nscoop_off, ws_allocs, ws_bytes)", key);
 }
 
 int wct_load_module(wct_ctx* ctx, int kind, int level, int n_layers, const wct_layer* layers, const float* c0w,
@@ -1554,6 +1619,7 @@ int wct_content_encode(wct_ctx* ctx, int level, const float* content, int H, int
     if (int rc = moments_impl(ctx, ctx->main, fC, C, h, w, x0, x1, sum, sumsq)) return rc;
   }
   ctx->cur_level = level; ctx->cur_h = h; ctx->cur_w = w; ctx->cur_H = H; ctx->cur_W = W;
+  ctx->pair_open = true;
   if (h_out) *h_out = h;
   if (w_out) *w_out = w;
   return WCT_OK;
@@ -1589,6 +1655,7 @@ int wct_content_decode(wct_ctx* ctx, int level, const double* M, const double* b
   }
   if (Ho) *Ho = ctx->cur_h << (level - 1);
   if (Wo) *Wo = ctx->cur_w << (level - 1);
+  ctx->pair_open = false;
   return range_readback(ctx);
 }
 
@@ -1960,30 +2027,13 @@ int wct_resize_u8_filter(wct_ctx* ctx, const uint8_t* src_hwc, int H, int W, uin
   return resize_impl(ctx, src_hwc, H, W, oH, oW, dst_hwc, planar, filter);
 }
 
-size_t wct_workspace_bytes(const wct_ctx* ctx, int H, int W, int Hs, int Ws) {
-  if (!ctx) return 0;
-  size_t act = 0, acts = 0, featc = 0, feats = 0, mom = 0;
-  for (int level = 1; level <= 5; ++level) {
-    const Module& e = ctx->mod[WCT_KIND_ENC][level];
-    const Module& d = ctx->mod[WCT_KIND_DEC][level];
-    if (!e.loaded || !d.loaded) continue;
-    int h, w, hs, ws;
-    level_dims(level, H, W, h, w);
-    level_dims(level, Hs, Ws, hs, ws);
-    const int C = e.layers.back().d.cout;
-    act = std::max(act, std::max(max_act_bytes(e, H, W, true), max_act_bytes(d, h, w, false)));
-    acts = std::max(acts, max_act_bytes(e, Hs, Ws, true));
-    featc = std::max(featc, (size_t)h * w * C * sizeof(float));
-    feats = std::max(feats, (size_t)hs * ws * C * sizeof(float));
-    mom = std::max(mom, moments_workspace_bytes(C, (long)h * w) + moments_workspace_bytes(C, (long)hs * ws));
-  }
-  return 2 * act + 2 * acts + featc + feats + mom + (size_t)3 * H * W * sizeof(float) + SMALL_BYTES + 2 * SUMS_BYTES +
-         6 * eig_result_bytes(512) + assemble_workspace_bytes(512);
-}
+}  // extern "C"
 
-int wct_reserve(wct_ctx* ctx, int H, int W, int Hs, int Ws) {
-  if (!ctx) return WCT_ERR_INVALID;
-  WCT_GUARD(ctx);
+namespace {
+// What a wct_stylize / wct_stylize_prepared (with its wct_style_prepare) of this size needs of every workspace buffer it touches, under the
+// context's current switches: the ONE list behind wct_workspace_bytes and wct_reserve (a buffer may appear more than once: the largest counts).
+struct WsNeed { DevBuf* buf; size_t bytes; };
+void workspace_plan(wct_ctx* ctx, int H, int W, int Hs, int Ws, std::vector<WsNeed>& need) {
   size_t act = 0, acts = 0, featc = 0, feats = 0, momc = 0, moms = 0;
   int cmax = 2;
   for (int level = 1; level <= 5; ++level) {
@@ -1997,36 +2047,66 @@ int wct_reserve(wct_ctx* ctx, int H, int W, int Hs, int Ws) {
     cmax = std::max(cmax, C);
     act = std::max(act, std::max(max_act_bytes(e, H, W, true), max_act_bytes(d, h, w, false)));
     acts = std::max(acts, max_act_bytes(e, Hs, Ws, true));
-    featc = std::max(featc, (size_t)h * w * C * sizeof(float));
+    featc = std::max(featc, (size_t)h * w * C * sizeof(float));     // content_side / style_side size these for every level, fused or not
     feats = std::max(feats, (size_t)hs * ws * C * sizeof(float));
-    momc = std::max(momc, moments_workspace_bytes(C, (long)h * w));
-    moms = std::max(moms, moments_workspace_bytes(C, (long)hs * ws));
+    if (l1_fused(ctx, level)) {   // relu1_1 is never materialised: the fused moments kernel's partials, whatever the image size
+      momc = std::max(momc, l1_moments_workspace_bytes());
+      moms = std::max(moms, l1_moments_workspace_bytes());
+    } else {
+      momc = std::max(momc, moments_workspace_bytes(C, (long)h * w));
+      moms = std::max(moms, moments_workspace_bytes(C, (long)hs * ws));
+    }
     const LayerDev& l0 = d.layers[0];
-    if (int rc = ensure(ctx, ctx->foldW, ((size_t)l0.d.cin_chunks * 36 * l0.d.cout_pad * 4 + l0.d.cout_pad) * sizeof(float))) return rc;
-    if (int rc = ensure(ctx, ctx->foldW16, conv_f16_weight_bytes(l0.d.cin, l0.d.cout_pad, l0.d.cout_pad == 16 ? 10 : 9) + 64 + conv_phase_weight_bytes(l0.d.cin) +
-                                                512 * sizeof(unsigned))) return rc;
-    if (fast_fold_level(ctx, level))
-      if (int rc = ensure(ctx, ctx->foldS[level], fold_style_doubles(l0.d.cout, l0.d.cin) * sizeof(double))) return rc;
-    if (int rc = ensure(ctx, ctx->eigS[level], eig_result_bytes(C))) return rc;
+    need.push_back({&ctx->foldW, ((size_t)l0.d.cin_chunks * 36 * l0.d.cout_pad * 4 + l0.d.cout_pad) * sizeof(float)});
+    need.push_back({&ctx->foldW16, conv_f16_weight_bytes(l0.d.cin, l0.d.cout_pad, l0.d.cout_pad == 16 ? 10 : 9) + 64 + conv_phase_weight_bytes(l0.d.cin) +
+                                       512 * sizeof(unsigned)});
+    if (fast_fold_level(ctx, level)) need.push_back({&ctx->foldS[level], fold_style_doubles(l0.d.cout, l0.d.cin) * sizeof(double)});
+    need.push_back({&ctx->eigS[level], eig_result_bytes(C)});
   }
-  if (int rc = ensure(ctx, ctx->main.actA, act)) return rc;
-  if (int rc = ensure(ctx, ctx->main.actB, act)) return rc;
-  if (int rc = ensure(ctx, ctx->side.actA, acts)) return rc;
-  if (int rc = ensure(ctx, ctx->side.actB, acts)) return rc;
-  if (int rc = ensure(ctx, ctx->featC, featc)) return rc;
-  if (int rc = ensure(ctx, ctx->featS, feats)) return rc;
-  if (int rc = ensure(ctx, ctx->main.wsMom, momc)) return rc;
-  if (int rc = ensure(ctx, ctx->side.wsMom, moms)) return rc;
-  if (int rc = ensure(ctx, ctx->tmpT, (size_t)3 * H * W * sizeof(float))) return rc;
-  if (int rc = ensure(ctx, ctx->eigC, eig_result_bytes(cmax))) return rc;
-  if (int rc = ensure(ctx, ctx->wsAsm, assemble_workspace_bytes(cmax))) return rc;
+  need.push_back({&ctx->main.actA, act});
+  need.push_back({&ctx->main.actB, act});
+  need.push_back({&ctx->side.actA, acts});
+  need.push_back({&ctx->side.actB, acts});
+  need.push_back({&ctx->featC, featc});
+  need.push_back({&ctx->featS, feats});
+  need.push_back({&ctx->main.wsMom, momc});
+  need.push_back({&ctx->side.wsMom, moms});
+  need.push_back({&ctx->tmpT, (size_t)3 * H * W * sizeof(float)});
+  need.push_back({&ctx->eigC, eig_result_bytes(cmax)});
+  need.push_back({&ctx->wsAsm, assemble_workspace_bytes(cmax)});
   for (Lane* ln : {&ctx->main, &ctx->side}) {
-    if (int rc = ensure(ctx, ln->wsEig, eig_workspace_bytes(cmax))) return rc;
-    SumsView sv;
-    if (int rc = sums_view(ctx, *ln, sv)) return rc;
+    need.push_back({&ln->wsEig, eig_workspace_bytes(cmax)});
+    need.push_back({&ln->sums, SUMS_BYTES});
   }
-  double *M, *b;
-  return mb_view(ctx, &M, &b);
+  need.push_back({&ctx->small, SMALL_BYTES});
+}
+}  // namespace
+
+extern "C" {
+
+size_t wct_workspace_bytes(const wct_ctx* cctx, int H, int W, int Hs, int Ws) {
+  if (!cctx) return 0;
+  wct_ctx* ctx = const_cast<wct_ctx*>(cctx);   // the plan names the context's buffers; nothing is modified
+  WCT_GUARD(ctx);
+  std::vector<WsNeed> need;
+  workspace_plan(ctx, H, W, Hs, Ws, need);
+  std::map<DevBuf*, size_t> per;
+  for (const WsNeed& n : need) per[n.buf] = std::max(per[n.buf], n.bytes);
+  size_t total = 0;
+  for (const auto& kv : per)
+    if (kv.second) total += (kv.second + 255) & ~(size_t)255;    // ensure()'s rounding
+  return total;
+}
+
+int wct_reserve(wct_ctx* ctx, int H, int W, int Hs, int Ws) {
+  if (!ctx) return WCT_ERR_INVALID;
+  WCT_GUARD(ctx);
+  std::vector<WsNeed> need;
+  workspace_plan(ctx, H, W, Hs, Ws, need);
+  for (const WsNeed& n : need)
+    if (n.bytes)
+      if (int rc = ensure(ctx, *n.buf, n.bytes)) return rc;
+  return WCT_OK;
 }
 
 int wct_set_numpy_variant(wct_ctx* ctx, int on) {

@@ -73,7 +73,15 @@ int wct_version(void);
 int wct_create(int device, wct_ctx** out);
 void wct_destroy(wct_ctx* ctx);
 const char* wct_last_error(const wct_ctx* ctx);
-int wct_set_stream(wct_ctx* ctx, void* hip_stream); /* hipStream_t; NULL = default stream */
+/* hipStream_t; NULL = default stream.  Binding a DIFFERENT stream orders it behind the old one: the new stream waits (by an event, no
+ * host synchronisation) for everything the context has enqueued on the previous stream, because calls under two streams share the
+ * context's workspace.  So consecutive calls of one context issued under different streams run in issue order and return what they
+ * return on one stream; they do not overlap each other (use two contexts for that).  The previous stream must still exist when the
+ * next one is bound.  Re-binding the stream already bound costs nothing.  A stream that is being captured into a HIP graph is bound
+ * without that dependency (synchronise before the capture begins, as torch.cuda.graph does).  A captured graph holds the workspace's
+ * addresses: replaying it after a later call has GROWN the workspace (wct_debug_get "ws_allocs" moved) reads and writes freed memory --
+ * capture after wct_reserve or a warm-up call of the largest size, and re-capture whenever the workspace has grown. */
+int wct_set_stream(wct_ctx* ctx, void* hip_stream);
 /* waits for both of the context's streams; returns WCT_ERR_RANGE -- ONCE, clearing the flag -- when an activation was clamped
  * since the last report (below), so a later WCT_ERR_RANGE always means a later clamp */
 int wct_sync(wct_ctx* ctx);
@@ -104,12 +112,25 @@ int wct_range_flag_f64(wct_ctx* ctx, double* flag_dev);
  * functions are SKIPPED and stale results reused) is a timing experiment that produces wrong pictures by design: it is refused
  * unless the environment variable WCT_DEBUG is set; so is "shard_emulate" (100 * ranks + rank: a context holding a ONE-rank communicator runs
  * wct_stylize_sharded with the geometry of one rank of a larger job, its peers being itself -- what one rank of the job executes, with
- * other numbers; 0: off).  Environment variables WCT_* are honoured only when WCT_DEBUG is set. */
+ * other numbers; 0: off).  Environment variables WCT_* are honoured only when WCT_DEBUG is set.
+ * "poison" (a byte 0..255, or -1 = off) is the test hook for "does a call read what an earlier call left in the workspace": it
+ * synchronises both of the context's streams, fills every allocated SCRATCH buffer of the context with that byte and, until it is
+ * turned off, every buffer the workspace allocates later as well (a grown buffer is a fresh allocation and usually zero pages).
+ * Scratch is every workspace buffer whose contents no later call is documented to read.  STATE survives a poison: module weights
+ * and their packed forms, the prepared style statistics of every level and their style-side folds (wct_style_prepare*,
+ * wct_style_import, wct_style_blend, wct_stylize_interp), the K style slots of the regions / blend calls, the resize weight
+ * tables, the counters -- and the content feature map / image copy held between wct_content_encode and the wct_content_decode
+ * that closes the pair (poison BEFORE wct_content_encode, not inside the pair; a second wct_content_decode of one encode is no
+ * longer covered).  A correct library returns the same bits with and without a poison; nothing is added to any call path but one
+ * branch where the workspace allocates (tests/test_state_gpu.py). */
 int wct_debug_set(wct_ctx* ctx, const char* key, double value);
 /* Health counters of the context (no reference counterpart): "nscoop_solves" = single-launch C = 128 matrix-function solves enqueued,
  * "nscoop_aborts" = those that aborted into the Jacobi net (watchdog / placement; synchronises the context), "nscoop_off" = bit mask
  * of lanes (1 main, 2 side) that went back to the multi-launch schedule because at least three and at least a quarter of their
- * single-launch solves aborted.  An aborted solve is repaired (same results) but costs ~7 ms: this is how that shows. */
+ * single-launch solves aborted.  An aborted solve is repaired (same results) but costs ~7 ms: this is how that shows.
+ * Workspace accounting: "ws_allocs" = device allocations the growing workspace has made so far (unchanged across a call = that call
+ * allocated nothing), "ws_bytes" = sum of the capacities of all workspace buffers now (weights, resize tables and counters not
+ * included). */
 int wct_debug_get(wct_ctx* ctx, const char* key, double* value);
 
 /* replaces SmallEncoder{L}_16x_aux(path) / SmallDecoder{L}_16x(path) / Encoder{L} / Decoder{L} construction
@@ -364,7 +385,14 @@ int wct_apply_mixed(wct_ctx* ctx, const float* feat, int C, int h, int w, int la
  *   wct_style_export / wct_style_import  move them (device f64: C*C matrix, then C means; wct_style_stats_count
  *                         doubles) so that the GPUs of a node compute each level ONCE and broadcast it
  *                         (wct_hip/sharded.py) instead of every rank repeating all five.
- * wct_style_prepare_levels: like wct_style_prepare for the levels in `level_mask` (bit L set = level L). */
+ * wct_style_prepare_levels: like wct_style_prepare for the levels in `level_mask` (bit L set = level L).
+ * Lifetime of the prepared statistics: there is ONE prepared slot per level.  It is rewritten by everything that computes or installs
+ * single-style statistics -- wct_style_prepare(_levels), wct_style_import, wct_style_blend, wct_style_solve, wct_stylize,
+ * wct_stylize_u8, wct_style_transfer_level (its level only), wct_synthesize with a texture, wct_stylize_interp (the blend of its
+ * styles), the sharded calls -- and then holds THAT style.  It survives everything else, bit for bit: wct_stylize_prepared,
+ * wct_synthesize without a texture, wct_stylize_regions and wct_stylize_blend (their K styles live in slots of their own), the
+ * split content calls, the un-fused entry points, the mode switches, wct_reserve, and a wct_load_module of a DECODER (the style-side
+ * fold of the old decoder is dropped and rebuilt from the kept statistics; after loading another ENCODER prepare again). */
 int wct_style_prepare_levels(wct_ctx* ctx, const float* style, int Hs, int Ws, unsigned level_mask);
 int wct_style_stats_count(const wct_ctx* ctx, int level, size_t* n_doubles);
 int wct_style_export(wct_ctx* ctx, int level, double* stats);
@@ -434,8 +462,14 @@ int wct_resize_u8(wct_ctx* ctx, const uint8_t* src_hwc, int H, int W, uint8_t* d
 int wct_resize_u8_to_planar(wct_ctx* ctx, const uint8_t* src_hwc, int H, int W, float* planar, int oH, int oW);
 int wct_resize_u8_filter(wct_ctx* ctx, const uint8_t* src_hwc, int H, int W, uint8_t* dst_hwc, float* planar, int oH, int oW, int filter);
 
-/* bytes of internal workspace a wct_stylize of this size will hold; wct_reserve allocates it up front (wct_synthesize's noise buffer,
- * 3*H*W floats, comes on top of both: see there) */
+/* wct_reserve allocates, up front, every workspace buffer that wct_stylize, wct_stylize_prepared and wct_style_prepare(_levels) of
+ * this content / style size touch, under the context's current mode switches: after it, those calls at this or any smaller size
+ * allocate nothing (wct_debug_get "ws_allocs" does not move), and a reserve of a smaller size is a no-op.  wct_workspace_bytes is
+ * meant EXACTLY: the bytes the workspace of a context that held nothing holds after wct_reserve of this size (wct_debug_get
+ * "ws_bytes"), which is also an upper bound of what the calls above alone would have made it hold.  Both come from one list in the
+ * library.  NOT covered -- these allocate on their first call of a size, on top: the fp32 staging of wct_stylize_u8, wct_synthesize's
+ * noise buffer (3*H*W floats, see there), the slots and maps of wct_stylize_regions / _interp / _blend, the layout and resize
+ * temporaries of the un-fused entry points. */
 size_t wct_workspace_bytes(const wct_ctx* ctx, int H, int W, int Hs, int Ws);
 int wct_reserve(wct_ctx* ctx, int H, int W, int Hs, int Ws);
 
