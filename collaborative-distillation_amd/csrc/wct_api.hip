@@ -2,6 +2,7 @@
 // 5-level cascade.  Host-side C++ only orchestrates launches on the context's HIP stream; all arithmetic is
 // in the kernels of conv3x3.hip / moments.hip / solve.hip / misc.hip.
 #include "../../include/wct_hip.h"
+#include "../../include/wct_hip_color.h"
 #include "wct_common.h"
 
 #include <cmath>
@@ -99,6 +100,9 @@ struct wct_ctx {
   std::vector<ResizeAxis> rsz_axes;   // weight tables per (in, out, filter), built on first use; least recently used evicted at 16
   unsigned long long rsz_clock = 0;
   DevBuf noise;       // wct_synthesize: the noise image (3 H W floats) the cascade reads as its content; kept until wct_destroy
+  // colour preservation (include/wct_hip_color.h): the matched style of wct_stylize_color (3 Hs Ws floats), its un-merged result (3 H W
+  // floats), and [sum_s 3 | sumsq_s 9 | sum_c 3 | sumsq_c 9 | A 9 | t 3 | pad to 64 doubles | stage-1 partials of the colour moments]
+  DevBuf colStyle, colOut, colWs;
   DevBuf l1img;       // level 1 fused: copy of the content image between wct_content_encode and wct_content_decode
   int cur_H = 0, cur_W = 0;
   int numpy_variant = 0;  // 1: `--numpy` semantics (util_wct.py:143): + I on the CONTENT covariance
@@ -165,7 +169,7 @@ struct wct_ctx {
   void each_buf(F&& f) {
     for (Lane* ln : {&main, &side})
       for (DevBuf* b : {&ln->actA, &ln->actB, &ln->wsMom, &ln->wsEig, &ln->sums}) f(*b, ln, true);
-    for (DevBuf* b : {&featS, &tmpT, &wsAsm, &small, &foldW, &foldW16, &eigC, &u8c, &u8s, &u8o, &rsz_tmp, &noise, &packed,
+    for (DevBuf* b : {&featS, &tmpT, &wsAsm, &small, &foldW, &foldW16, &eigC, &u8c, &u8s, &u8o, &rsz_tmp, &noise, &colStyle, &colOut, &colWs, &packed,
                       &shIn, &shOut, &shNext, &shEdge, &shStyle, &shStats, &shMb,
                       &regLab, &regHist, &regSums, &regMb, &regFeat, &wsRegMom, &wsRegApply,
                       &blendW, &blendStat, &wsBlendPool, &wsBlendApply})
@@ -1896,6 +1900,141 @@ int wct_synthesize(wct_ctx* ctx, const float* texture, int Ht, int Wt, int H, in
   if (int rc = noise_impl(ctx, seed, stream_id, H, W, noise)) return rc;
   if (texture) return stylize_impl(ctx, noise, H, W, texture, Ht, Wt, alpha, num_run, out, Ho, Wo);
   return stylize_prepared_impl(ctx, "synthesize", noise, H, W, alpha, num_run, out, Ho, Wo);
+}
+
+// ---- colour preservation (include/wct_hip_color.h; kernels in color.hip) ------------------------------------------------------------
+namespace {
+constexpr size_t COLOR_WS_HEAD = 64;   // doubles in front of the stage-1 partials: the two sides' sums and (A, t) of wct_color_match
+
+int color_ws(wct_ctx* ctx, long npix) { return ensure(ctx, ctx->colWs, COLOR_WS_HEAD * sizeof(double) + color_moments_workspace_bytes(npix)); }
+
+int color_moments_impl(wct_ctx* ctx, const float* planar, int H, int W, double* sum, double* sumsq) {
+  const long npix = (long)H * W;
+  if (int rc = color_ws(ctx, npix)) return rc;
+  ProfScope ps(ctx, ctx->main.stream, "color_moments", 18.0 * npix, 12.0 * npix);
+  HIPCHK(ctx, launch_color_moments(planar, npix, sum, sumsq, reinterpret_cast<double*>(ctx->colWs.p) + COLOR_WS_HEAD,
+                                   ctx->colWs.cap - COLOR_WS_HEAD * sizeof(double), ctx->main.stream));
+  return WCT_OK;
+}
+
+int color_solve_impl(wct_ctx* ctx, double n_c, const double* sum_c, const double* sumsq_c, double n_s, const double* sum_s, const double* sumsq_s,
+                     double eps, double* A, double* t) {
+  ProfScope ps(ctx, ctx->main.stream, "color_solve", 0, 36 * sizeof(double));
+  HIPCHK(ctx, launch_color_solve(n_c, sum_c, sumsq_c, n_s, sum_s, sumsq_s, eps, A, t, ctx->main.stream));
+  return WCT_OK;
+}
+
+int color_apply_impl(wct_ctx* ctx, const float* in, int H, int W, const double* A, const double* t, float* out) {
+  const long npix = (long)H * W;
+  ProfScope ps(ctx, ctx->main.stream, "color_apply", 18.0 * npix, 24.0 * npix);
+  HIPCHK(ctx, launch_color_apply(in, npix, A, t, out, ctx->main.stream));
+  return WCT_OK;
+}
+
+int color_match_impl(wct_ctx* ctx, const float* style, int Hs, int Ws, const float* content, int H, int W, float* style_out) {
+  const long ns = (long)Hs * Ws, nc = (long)H * W;
+  if (int rc = color_ws(ctx, ns > nc ? ns : nc)) return rc;   // both sides' partials fit BEFORE the first sums are written: the head never moves
+  double* hd = reinterpret_cast<double*>(ctx->colWs.p);
+  double *sum_s = hd, *sumsq_s = hd + 3, *sum_c = hd + 12, *sumsq_c = hd + 15, *A = hd + 24, *t = hd + 33;
+  if (int rc = color_moments_impl(ctx, style, Hs, Ws, sum_s, sumsq_s)) return rc;
+  if (int rc = color_moments_impl(ctx, content, H, W, sum_c, sumsq_c)) return rc;
+  if (int rc = color_solve_impl(ctx, (double)nc, sum_c, sumsq_c, (double)ns, sum_s, sumsq_s, WCT_COLOR_EPS, A, t)) return rc;
+  return color_apply_impl(ctx, style, Hs, Ws, A, t, style_out);
+}
+
+int luma_merge_impl(wct_ctx* ctx, const float* stylised, int Ho, int Wo, const float* content, int Hc, int Wc, float* out_planar, uint8_t* out_hwc,
+                    int round_mode) {
+  ProfScope ps(ctx, ctx->main.stream, "luma_merge", 14.0 * Ho * Wo, (out_planar ? 36.0 : 27.0) * Ho * Wo);
+  HIPCHK(ctx, launch_luma_merge(stylised, Ho, Wo, content, Hc, Wc, out_planar, out_hwc, round_mode, ctx->main.stream));
+  return WCT_OK;
+}
+}  // namespace
+
+int wct_color_moments(wct_ctx* ctx, const float* planar, int H, int W, double* sum, double* sumsq) {
+  if (!ctx) return WCT_ERR_INVALID;
+  WCT_GUARD(ctx);
+  if (!planar || !sum || !sumsq || H < 1 || W < 1)
+    return fail(ctx, WCT_ERR_INVALID, "wct_color_moments: bad arguments (%dx%d, planar %s, sum %s, sumsq %s)", H, W, planar ? "given" : "NULL",
+                sum ? "given" : "NULL", sumsq ? "given" : "NULL");
+  if ((long)H * W > color_moments_max_pixels())
+    return fail(ctx, WCT_ERR_INVALID, "wct_color_moments: %dx%d exceeds the %ld pixels the summation contract covers", H, W, color_moments_max_pixels());
+  return color_moments_impl(ctx, planar, H, W, sum, sumsq);
+}
+
+int wct_color_solve(wct_ctx* ctx, double n_c, const double* sum_c, const double* sumsq_c, double n_s, const double* sum_s, const double* sumsq_s,
+                    double eps, double* A, double* t) {
+  if (!ctx) return WCT_ERR_INVALID;
+  WCT_GUARD(ctx);
+  if (!sum_c || !sumsq_c || !sum_s || !sumsq_s || !A || !t) return fail(ctx, WCT_ERR_INVALID, "wct_color_solve: NULL argument");
+  if (!(n_c >= 2.0) || !(n_s >= 2.0) || !std::isfinite(n_c) || !std::isfinite(n_s))
+    return fail(ctx, WCT_ERR_INVALID, "wct_color_solve: at least 2 pixels on either side expected, got n_c = %g, n_s = %g", n_c, n_s);
+  if (!std::isfinite(eps) || !(eps > 0.0)) return fail(ctx, WCT_ERR_INVALID, "wct_color_solve: eps must be finite and positive, got %g", eps);
+  return color_solve_impl(ctx, n_c, sum_c, sumsq_c, n_s, sum_s, sumsq_s, eps, A, t);
+}
+
+int wct_color_apply(wct_ctx* ctx, const float* in, int H, int W, const double* A, const double* t, float* out) {
+  if (!ctx) return WCT_ERR_INVALID;
+  WCT_GUARD(ctx);
+  if (!in || !A || !t || !out || H < 1 || W < 1) return fail(ctx, WCT_ERR_INVALID, "wct_color_apply: bad arguments (%dx%d, or a NULL pointer)", H, W);
+  return color_apply_impl(ctx, in, H, W, A, t, out);
+}
+
+int wct_color_match(wct_ctx* ctx, const float* style, int Hs, int Ws, const float* content, int H, int W, float* style_out) {
+  if (!ctx) return WCT_ERR_INVALID;
+  WCT_GUARD(ctx);
+  if (!style || !content || !style_out) return fail(ctx, WCT_ERR_INVALID, "wct_color_match: NULL argument");
+  if (Hs < 1 || Ws < 1 || H < 1 || W < 1 || (long)Hs * Ws < 2 || (long)H * W < 2)
+    return fail(ctx, WCT_ERR_INVALID, "wct_color_match: at least 2 pixels on either side expected, got style %dx%d, content %dx%d", Hs, Ws, H, W);
+  if ((long)Hs * Ws > color_moments_max_pixels() || (long)H * W > color_moments_max_pixels())
+    return fail(ctx, WCT_ERR_INVALID, "wct_color_match: style %dx%d or content %dx%d exceeds the %ld pixels the summation contract covers", Hs, Ws, H, W,
+                color_moments_max_pixels());
+  return color_match_impl(ctx, style, Hs, Ws, content, H, W, style_out);
+}
+
+int wct_luma_merge(wct_ctx* ctx, const float* stylised, int Ho, int Wo, const float* content, int Hc, int Wc, float* out_planar, uint8_t* out_hwc,
+                   int round_mode) {
+  if (!ctx) return WCT_ERR_INVALID;
+  WCT_GUARD(ctx);
+  if (!stylised || !content) return fail(ctx, WCT_ERR_INVALID, "wct_luma_merge: NULL image");
+  if ((out_planar != nullptr) == (out_hwc != nullptr))
+    return fail(ctx, WCT_ERR_INVALID, "wct_luma_merge: exactly one of out_planar and out_hwc expected, got %s", out_planar ? "both" : "neither");
+  if (Ho < 1 || Wo < 1 || Ho > Hc || Wo > Wc)
+    return fail(ctx, WCT_ERR_INVALID, "wct_luma_merge: result %dx%d must be non-empty and no larger than the content %dx%d", Ho, Wo, Hc, Wc);
+  if (round_mode != 0 && round_mode != 1) return fail(ctx, WCT_ERR_INVALID, "wct_luma_merge: round_mode 0 or 1 expected, got %d", round_mode);
+  return luma_merge_impl(ctx, stylised, Ho, Wo, content, Hc, Wc, out_planar, out_hwc, round_mode);
+}
+
+int wct_stylize_color(wct_ctx* ctx, const float* content, int H, int W, const float* style, int Hs, int Ws, float alpha, int num_run, int mode,
+                      float* out, int* Ho, int* Wo) {
+  if (!ctx) return WCT_ERR_INVALID;
+  WCT_GUARD(ctx);
+  if (!content || !style || !out || num_run < 1) return fail(ctx, WCT_ERR_INVALID, "wct_stylize_color: bad arguments (a NULL pointer, or num_run < 1)");
+  if (mode < 1 || mode > 3)
+    return fail(ctx, WCT_ERR_INVALID, "wct_stylize_color: mode %d is not WCT_COLOR_MATCH (1), WCT_COLOR_LUMA (2) or both (3)", mode);
+  if (H < 1 || W < 1 || Hs < 1 || Ws < 1 || ((mode & WCT_COLOR_MATCH) && ((long)Hs * Ws < 2 || (long)H * W < 2)))
+    return fail(ctx, WCT_ERR_INVALID, "wct_stylize_color: bad shapes (content %dx%d, style %dx%d)", H, W, Hs, Ws);
+  if ((mode & WCT_COLOR_MATCH) && ((long)Hs * Ws > color_moments_max_pixels() || (long)H * W > color_moments_max_pixels()))
+    return fail(ctx, WCT_ERR_INVALID, "wct_stylize_color: style %dx%d or content %dx%d exceeds the %ld pixels the summation contract covers", Hs, Ws, H, W,
+                color_moments_max_pixels());
+  // every buffer first: a growing one synchronises, and nothing enqueued below may find its source moved
+  if (mode & WCT_COLOR_MATCH)
+    if (int rc = ensure(ctx, ctx->colStyle, (size_t)3 * Hs * Ws * sizeof(float))) return rc;
+  if (mode & WCT_COLOR_LUMA)
+    if (int rc = ensure(ctx, ctx->colOut, (size_t)3 * H * W * sizeof(float))) return rc;
+  const float* st = style;
+  if (mode & WCT_COLOR_MATCH) {
+    float* matched = reinterpret_cast<float*>(ctx->colStyle.p);
+    if (int rc = color_match_impl(ctx, style, Hs, Ws, content, H, W, matched)) return rc;
+    st = matched;   // the side lane reads it behind fork_side's event, and the cascade's last level has waited for the side lane
+  }
+  float* dst = (mode & WCT_COLOR_LUMA) ? reinterpret_cast<float*>(ctx->colOut.p) : out;
+  int ho = 0, wo = 0;
+  if (int rc = stylize_impl(ctx, content, H, W, st, Hs, Ws, alpha, num_run, dst, &ho, &wo)) return rc;
+  if (mode & WCT_COLOR_LUMA)
+    if (int rc = luma_merge_impl(ctx, dst, ho, wo, content, H, W, out, nullptr, 0)) return rc;
+  if (Ho) *Ho = ho;
+  if (Wo) *Wo = wo;
+  return WCT_OK;
 }
 
 int wct_u8_to_planar(wct_ctx* ctx, const uint8_t* hwc, int H, int W, float* planar) {

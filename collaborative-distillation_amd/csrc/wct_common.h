@@ -123,6 +123,18 @@ hipError_t launch_u8_to_planar(const uint8_t* hwc, long npix, float* planar, hip
 hipError_t launch_planar_to_u8(const float* planar, long npix, uint8_t* hwc, int round_mode, hipStream_t s);
 // ---- seeded uniform noise (noise.hip): planar 3 x H x W fp32 in [0, 1), Philox4x32-10 keyed by seed, values defined by position alone
 hipError_t launch_noise_uniform(unsigned long long seed, unsigned stream_id, int H, int W, float* planar, hipStream_t s);
+// ---- colour preservation (color.hip; include/wct_hip_color.h): fp64 raw colour moments of a planar image (stage-1 partials in `workspace`,
+//      a fixed-order second stage; the summation tree depends on npix alone), the 3 x 3 solve A = cov_c^(1/2) cov_s^(-1/2), t = mu_c - A mu_s
+//      (one thread, cyclic Jacobi), out_p = float(A x_p + t), and the luminance merge out_c = content_c + (Y(stylised) - Y(content))
+long color_moments_tiles(long npix);
+long color_moments_max_pixels();   // above it the second stage would add more than 4096 partials in sequence: refused by the API
+size_t color_moments_workspace_bytes(long npix);
+hipError_t launch_color_moments(const float* planar, long npix, double* sum, double* sumsq, void* workspace, size_t workspace_bytes, hipStream_t s);
+hipError_t launch_color_solve(double n_c, const double* sum_c, const double* sumsq_c, double n_s, const double* sum_s, const double* sumsq_s,
+                              double eps, double* A, double* t, hipStream_t s);
+hipError_t launch_color_apply(const float* in, long npix, const double* A, const double* t, float* out, hipStream_t s);
+hipError_t launch_luma_merge(const float* stylised, int Ho, int Wo, const float* content, int Hc, int Wc, float* out_planar, uint8_t* out_hwc,
+                             int round_mode, hipStream_t s);
 // *dst = (double)*counter on the stream (wct_range_flag_f64: the saturation counter as a value a sharded run can all-reduce)
 hipError_t launch_counter_to_f64(const unsigned* counter, double* dst, hipStream_t s);
 // ---- image edge: transforms.Resize = Pillow's bilinear resampler, bit-exact (resize.hip)

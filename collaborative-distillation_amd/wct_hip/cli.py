@@ -24,6 +24,10 @@ index in the listing as the stream id: Philox4x32-10, include/wct_hip.h) and mad
 is the cascade's, as in the reference: every edge a multiple of 16 (floor pooling, four times).  --synthesis_size is the size of the
 FILE: the noise is made at the next multiples of 16 and the result cropped (top left) to WxH.  Only the decoded texture goes to the
 GPU and only the uint8 result comes back.
+--preserve_color match | luma (not in the reference; Gatys et al. 2017, section 5) keeps the content's colours: `match` maps the style's
+colours onto the content's colour distribution before the cascade (per pair: wct_stylize_color, no style-statistics cache), `luma`
+keeps the content's chroma and takes the stylised luminance (wct_luma_merge fused with the uint8 conversion; also behind --maskPath
+and --interp_styles / --weightPath).  The files carry _color=<mode> in their names.
 Decoding/encoding files needs Pillow on the host (the reference's own dependency); the GPU library is mandatory: there
 is no CPU fallback.
 """
@@ -83,6 +87,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--synthesis_size", type=str, default=None,
                    help="WxH of the images --synthesis writes, exactly (default: noise of the texture's size after --style_size, as in the "
                         "reference, whose cascade floors every edge to a multiple of 16)")
+    # not in the reference: colour preservation (include/wct_hip_color.h)
+    p.add_argument("--preserve_color", type=str, default=None, choices=["match", "luma"],
+                   help="keep the content's colours: match = map the style's colours onto the content's colour distribution before "
+                        "stylisation, luma = keep the content's chroma and take only the stylised luminance")
     return p
 
 
@@ -119,6 +127,9 @@ def pair_name(content_file: str, style_file: str) -> str:
 
 def out_name(args, imname: str) -> str:
     """WCT.py:127 (str(1) for the integer default of --alpha, like '%s' % args.alpha there)."""
+    color = getattr(args, "preserve_color", None)
+    if color:      # --preserve_color: runs with and without the flag never collide
+        return os.path.join(args.outf, "%s_mode=%s_alpha=%s_color=%s_%s" % (args.log_mark, args.mode, args.alpha, color, imname))
     return os.path.join(args.outf, "%s_mode=%s_alpha=%s_%s" % (args.log_mark, args.mode, args.alpha, imname))
 
 
@@ -206,7 +217,7 @@ def run_regions(args, wct, content_dir, logprinter) -> float:
             res = wct.stylize_regions(c_f32, s32, lab, args.alpha, args.num_run)
             wct.sync()
             wct.set_conv_mode("f16x3")
-        out = wct.to_u8(res, args.round_mode).cpu().numpy()
+        out = _finish_u8(wct, args, res, c_f32).cpu().numpy()
         Image.fromarray(out).save(region_out_name(args, cfile))
         dt = time.time() - t0
         avg += dt
@@ -221,6 +232,29 @@ def check_region_args(args) -> None:
         n = len([p for p in args.region_styles.split(",") if p])
         if not 1 <= n <= 8:
             raise ValueError("--region_styles: 1 to 8 style images, got %d" % n)
+
+
+def check_color_args(args) -> None:
+    """--preserve_color: luma is a post-merge and goes with every content-driven mode; match needs ONE style per content."""
+    color = getattr(args, "preserve_color", None)
+    if color is None:
+        return
+    if color not in ("match", "luma"):
+        raise ValueError("--preserve_color: match or luma expected, got %r" % (color,))
+    if args.synthesis:
+        raise ValueError("--preserve_color does not mix with --synthesis: there is no content whose colours could be kept")
+    if color == "match":
+        for flag, name in ((args.maskPath, "--maskPath"), (args.interp_styles, "--interp_styles"), (args.weightPath, "--weightPath")):
+            if flag is not None:
+                raise ValueError("--preserve_color match does not mix with %s (several styles per content); use --preserve_color luma" % name)
+
+
+def _finish_u8(wct, args, res, c_f32):
+    """The result as uint8 HWC on the device: save_image's conversion, with --preserve_color luma fused into the luminance merge
+    against the content tensor the cascade was given."""
+    if getattr(args, "preserve_color", None) == "luma":
+        return wct.luma_merge(res, c_f32, u8=True, round_mode=args.round_mode)
+    return wct.to_u8(res, args.round_mode)
 
 
 def interp_style_list(args) -> List[str]:
@@ -337,7 +371,7 @@ def run_interp(args, wct, content_dir, logprinter) -> Tuple[float, int]:
             res = run(c_f32, s32, wmap)
             wct.sync()
             wct.set_conv_mode("f16x3")
-        out = wct.to_u8(res, args.round_mode).cpu().numpy()
+        out = _finish_u8(wct, args, res, c_f32).cpu().numpy()
         Image.fromarray(out).save(interp_out_name(args, cfile, blend))
         dt = time.time() - t0
         avg += dt
@@ -460,10 +494,14 @@ def _to_tensor(wct, u8, size):
 
 def _fp32_fallback(wct, args, logprinter, c_f32, style_u8_dev):
     """An activation left the f16x3 range (+-65504) and was clamped: a deviation from the fp32 reference -- never silent.
-    Recompute this pair with the exact-fp32 convolutions (style statistics included)."""
+    Recompute this pair with the exact-fp32 convolutions (style statistics included), under the same colour control (--preserve_color
+    match here; luma is applied by the caller's _finish_u8)."""
     logprinter("WARNING: f16x3 range exceeded for this pair -> recomputing it with exact-fp32 convolutions")
     wct.set_conv_mode("fp32")
-    res = wct.stylize(c_f32, _to_tensor(wct, style_u8_dev, args.style_size), args.alpha, args.num_run)
+    if getattr(args, "preserve_color", None) == "match":
+        res = wct.stylize_color(c_f32, _to_tensor(wct, style_u8_dev, args.style_size), "match", args.alpha, args.num_run)
+    else:
+        res = wct.stylize(c_f32, _to_tensor(wct, style_u8_dev, args.style_size), args.alpha, args.num_run)
     wct.sync()
     wct.set_conv_mode("f16x3")
     return res
@@ -477,29 +515,40 @@ def run_serial(args, wct, pairs, content_dir, style_dir, logprinter) -> float:
     # style statistics are computed once per style image and reused for every content it is paired with
     # (data_loader.py:32-36 builds the content x style product; the reference re-encodes the style for every pair)
     style_cache = {}
+    # --preserve_color match: the matched style depends on the content, so there are no statistics to cache -- every pair matches and
+    # prepares its own style (wct_stylize_color); the decoded style stays on the device (uint8, the last few) instead
+    match = getattr(args, "preserve_color", None) == "match"
+    style_dev = {}
     for i, (cfile, sfile) in enumerate(pairs):
         imname = pair_name(cfile, sfile)
         logprinter("\n" + "*" * 30 + ' #%s: Transferring "%s"' % (i, imname))
         # decoded uint8 frames cross PCIe as they are (3 B/px, pinned); Resize and ToTensor run on the GPU
         c_u8 = torch.from_numpy(load_rgb_u8(os.path.join(content_dir, cfile))).pin_memory().cuda(non_blocking=True)
-        s_u8 = None
-        if sfile not in style_cache:
+        s_u8 = style_dev.get(sfile) if match else None
+        if s_u8 is None and (match or sfile not in style_cache):
             s_u8 = torch.from_numpy(load_rgb_u8(os.path.join(style_dir, sfile))).pin_memory().cuda(non_blocking=True)
         t0 = time.time()
-        if s_u8 is not None:
+        if match:
+            style_dev[sfile] = s_u8
+            while len(style_dev) > 8:
+                style_dev.pop(next(iter(style_dev)))
+            c_f32 = _to_tensor(wct, c_u8, args.content_size)
+            res = wct.stylize_color(c_f32, _to_tensor(wct, s_u8, args.style_size), "match", args.alpha, args.num_run)
+        elif s_u8 is not None:
             wct.style_prepare(_to_tensor(wct, s_u8, args.style_size))
             style_cache[sfile] = {L: wct.style_export(L) for L in (5, 4, 3, 2, 1)}
         else:
             for L, stats in style_cache[sfile].items():
                 wct.style_import(L, stats)
-        c_f32 = _to_tensor(wct, c_u8, args.content_size)
-        res = wct.stylize_prepared(c_f32, args.alpha, args.num_run)
+        if not match:
+            c_f32 = _to_tensor(wct, c_u8, args.content_size)
+            res = wct.stylize_prepared(c_f32, args.alpha, args.num_run)
         if wct.saturation_count(reset=True):
             if s_u8 is None:
                 s_u8 = torch.from_numpy(load_rgb_u8(os.path.join(style_dir, sfile))).cuda()
             res = _fp32_fallback(wct, args, logprinter, c_f32, s_u8)
             style_cache.pop(sfile, None)          # its cached statistics may carry the clamp too
-        out = wct.to_u8(res, args.round_mode).cpu().numpy()   # .cpu() syncs
+        out = _finish_u8(wct, args, res, c_f32).cpu().numpy()   # .cpu() syncs
         Image.fromarray(out).save(out_name(args, imname))
         dt = time.time() - t0
         avg += dt
@@ -535,6 +584,7 @@ def run_pipelined(args, wct, pairs, content_dir, style_dir, logprinter) -> float
         Image.fromarray(rec["host"].numpy()).save(rec["path"])
         return time.time()
 
+    match = getattr(args, "preserve_color", None) == "match"     # per-pair matched styles (wct_stylize_color): no statistics cache, style_dev is the cache
     strict = wct.strict_range
     wct.strict_range = False                          # the flag is read per pair below, never raised in the middle of the window
     t_start = time.time()
@@ -553,7 +603,7 @@ def run_pipelined(args, wct, pairs, content_dir, style_dir, logprinter) -> float
             cfile, sfile = pairs[j]
             if ("c", cfile) not in fut:
                 fut[("c", cfile)] = dec.submit(decode, os.path.join(content_dir, cfile))
-            if sfile not in style_cache and ("s", sfile) not in fut:
+            if sfile not in (style_dev if match else style_cache) and ("s", sfile) not in fut:
                 fut[("s", sfile)] = dec.submit(decode, os.path.join(style_dir, sfile))
         live = {("c", pairs[j][0]) for j in range(i, min(n, i + ahead))} | {("s", pairs[j][1]) for j in range(i, min(n, i + ahead))}
         for k in [k for k in fut if k not in live]:
@@ -574,7 +624,7 @@ def run_pipelined(args, wct, pairs, content_dir, style_dir, logprinter) -> float
             if s_u8 is None:
                 s_u8 = torch.from_numpy(load_rgb_u8(os.path.join(style_dir, sfile))).cuda()
             res = _fp32_fallback(wct, args, logprinter, rec["c_f32"], s_u8)
-            rec["host"].copy_(wct.to_u8(res, args.round_mode))
+            rec["host"].copy_(_finish_u8(wct, args, res, rec["c_f32"]))
             rec["ev"] = torch.cuda.Event()
             rec["ev"].record()
             # the reset above acknowledged EVERY clamp so far, also one inside a style_prepare of a discarded pair (index > i): statistics
@@ -614,7 +664,14 @@ def run_pipelined(args, wct, pairs, content_dir, style_dir, logprinter) -> float
             imname = pair_name(cfile, sfile)
             logprinter("\n" + "*" * 30 + ' #%s: Transferring "%s"' % (i, imname))
             c_u8 = fut[("c", cfile)].result().cuda(non_blocking=True)
-            if sfile not in style_cache:
+            if match:
+                s_u8 = style_dev.pop(sfile, None)
+                if s_u8 is None:
+                    s_u8 = fut[("s", sfile)].result().cuda(non_blocking=True)
+                style_dev[sfile] = s_u8                     # (re-inserted: most recently used last)
+                while len(style_dev) > depth + 2:
+                    style_dev.pop(next(iter(style_dev)))
+            elif sfile not in style_cache:
                 s_u8 = fut[("s", sfile)].result().cuda(non_blocking=True)
                 style_dev[sfile] = s_u8
                 while len(style_dev) > depth + 2:           # the fallback reloads a style it no longer finds here: keep the few that can be in flight
@@ -626,8 +683,13 @@ def run_pipelined(args, wct, pairs, content_dir, style_dir, logprinter) -> float
                 for L, stats in style_cache[sfile].items():
                     wct.style_import(L, stats)
             c_f32 = _to_tensor(wct, c_u8, args.content_size)
-            res = wct.stylize_prepared(c_f32, args.alpha, args.num_run)
-            out_dev = wct.to_u8(res, args.round_mode)
+            if match:
+                s_f32 = _to_tensor(wct, s_u8, args.style_size)
+                res = wct.stylize_color(c_f32, s_f32, "match", args.alpha, args.num_run)
+            else:
+                s_f32 = None
+                res = wct.stylize_prepared(c_f32, args.alpha, args.num_run)
+            out_dev = _finish_u8(wct, args, res, c_f32)
             host = torch.empty(out_dev.shape, dtype=torch.uint8, pin_memory=True)
             host.copy_(out_dev, non_blocking=True)
             flag_host = torch.zeros(1, dtype=torch.float64).pin_memory()
@@ -635,7 +697,7 @@ def run_pipelined(args, wct, pairs, content_dir, style_dir, logprinter) -> float
             ev = torch.cuda.Event()
             ev.record()
             inflight.append({"i": i, "imname": imname, "path": out_name(args, imname), "host": host, "flag_host": flag_host, "ev": ev,
-                             "sfile": sfile, "c_f32": c_f32, "keep": (out_dev, res, c_u8)})
+                             "sfile": sfile, "c_f32": c_f32, "keep": (out_dev, res, c_u8, s_f32)})
         for w in writes:
             w.result()
     finally:
@@ -651,6 +713,7 @@ def main(argv: Optional[List[str]] = None) -> int:
     check_region_args(args)
     check_interp_args(args)
     check_synthesis_args(args)
+    check_color_args(args)
     os.makedirs(args.outf, exist_ok=True)
     logprinter = LogPrinter(args.debug, os.path.join(args.outf, "log_%s_%s.txt" % (args.log_mark, args.mode)))
     logprinter(sorted(vars(args).items()))

@@ -32,6 +32,12 @@ SYMBOLS = [
     "wct_workspace_bytes", "wct_reserve", "wct_set_conv_mode", "wct_set_numpy_variant", "wct_set_overlap", "wct_profile_enable", "wct_profile_reset", "wct_profile_read",
 ]
 
+# every symbol include/wct_hip_color.h declares (colour preservation); bound from the same libwct_hip.so
+SYMBOLS_COLOR = ["wct_color_moments", "wct_color_solve", "wct_color_apply", "wct_color_match", "wct_luma_merge", "wct_stylize_color"]
+COLOR_MATCH, COLOR_LUMA = 1, 2                                      # WCT_COLOR_*: the mode mask of wct_stylize_color
+COLOR_MODES = {"match": COLOR_MATCH, "luma": COLOR_LUMA, "match+luma": COLOR_MATCH | COLOR_LUMA}
+COLOR_EPS = 1e-5                                                    # WCT_COLOR_EPS
+
 
 class WctLayer(ctypes.Structure):
     _fields_ = [("cin", c_int), ("cout", c_int), ("pool_after", c_int), ("up_after", c_int),
@@ -152,6 +158,12 @@ def load() -> ctypes.CDLL:
     lib.wct_resize_u8_filter.argtypes = [c_void_p, vp, c_int, c_int, vp, vp, c_int, c_int, c_int]
     lib.wct_noise_uniform.argtypes = [c_void_p, ctypes.c_uint64, ctypes.c_uint32, c_int, c_int, vp]
     lib.wct_synthesize.argtypes = [c_void_p, vp, c_int, c_int, c_int, c_int, ctypes.c_uint64, ctypes.c_uint32, c_float, c_int, vp, ip, ip]
+    lib.wct_color_moments.argtypes = [c_void_p, vp, c_int, c_int, vp, vp]
+    lib.wct_color_solve.argtypes = [c_void_p, c_double, vp, vp, c_double, vp, vp, c_double, vp, vp]
+    lib.wct_color_apply.argtypes = [c_void_p, vp, c_int, c_int, vp, vp, vp]
+    lib.wct_color_match.argtypes = [c_void_p, vp, c_int, c_int, vp, c_int, c_int, vp]
+    lib.wct_luma_merge.argtypes = [c_void_p, vp, c_int, c_int, vp, c_int, c_int, vp, vp, c_int]
+    lib.wct_stylize_color.argtypes = [c_void_p, vp, c_int, c_int, vp, c_int, c_int, c_float, c_int, c_int, vp, ip, ip]
     lib.wct_workspace_bytes.argtypes = [c_void_p, c_int, c_int, c_int, c_int]
     lib.wct_workspace_bytes.restype = c_size_t
     lib.wct_reserve.argtypes = [c_void_p, c_int, c_int, c_int, c_int]

@@ -717,6 +717,105 @@ class WCT:
         self._style_keep = t      # the side stream reads it asynchronously
         return out.view(-1)[: 3 * ho.value * wo.value].view(1, 3, ho.value, wo.value)
 
+    # ------------------------------------------------------------------ colour preservation (include/wct_hip_color.h)
+    def _out_like(self, out: Optional[torch.Tensor], what: str, numel: int, dtype=torch.float32) -> Optional[torch.Tensor]:
+        """A caller-provided result buffer with exactly `numel` values (contiguous, this device; a view is fine), or None."""
+        if out is not None and (out.dtype != dtype or not out.is_cuda or out.device.index != self.device or not out.is_contiguous()
+                                or out.numel() != numel):
+            raise ValueError("%s: out must be a contiguous %s tensor on cuda:%d with %d values" % (what, dtype, self.device, numel))
+        return out
+
+    @torch.no_grad()
+    def color_moments(self, img: torch.Tensor):
+        """Raw fp64 colour sums of a [1,3,H,W] / [3,H,W] image over all its pixels: (n, sum[3], sumsq[3,3]) (wct_color_moments).
+        The summation tree depends on (H, W) alone: bitwise reproducible across calls, alignments and contexts."""
+        x = self._img(img)
+        H, W = int(x.shape[1]), int(x.shape[2])
+        s = torch.empty(3, device=x.device, dtype=torch.float64)
+        ss = torch.empty(3, 3, device=x.device, dtype=torch.float64)
+        self._stream()
+        self._chk(self._lib.wct_color_moments(self._ctx, x.data_ptr(), H, W, s.data_ptr(), ss.data_ptr()))
+        return float(H * W), s, ss
+
+    @torch.no_grad()
+    def color_solve(self, n_c, sum_c, sumsq_c, n_s, sum_s, sumsq_s, eps: float = _lib.COLOR_EPS):
+        """(n, sum, sumsq) of content and style -> (A [3,3], t [3]) fp64 on the device: A = cov_c^(1/2) cov_s^(-1/2) with unbiased
+        covariances + eps I, t = mu_c - A mu_s (wct_color_solve; no host synchronisation)."""
+        sum_c, sumsq_c = self._dev_f64(sum_c, 3, "sum_c"), self._dev_f64(sumsq_c, 9, "sumsq_c")
+        sum_s, sumsq_s = self._dev_f64(sum_s, 3, "sum_s"), self._dev_f64(sumsq_s, 9, "sumsq_s")
+        A = torch.empty(3, 3, device=sum_c.device, dtype=torch.float64)
+        t = torch.empty(3, device=sum_c.device, dtype=torch.float64)
+        self._stream()
+        self._chk(self._lib.wct_color_solve(self._ctx, float(n_c), sum_c.data_ptr(), sumsq_c.data_ptr(), float(n_s), sum_s.data_ptr(),
+                                            sumsq_s.data_ptr(), float(eps), A.data_ptr(), t.data_ptr()))
+        return A, t
+
+    @torch.no_grad()
+    def color_apply(self, img: torch.Tensor, A: torch.Tensor, t: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """out_p = float(A x_p + t) per pixel, evaluated in fp64, not clamped (wct_color_apply).  `out` may be `img` itself."""
+        x = self._img(img)
+        H, W = int(x.shape[1]), int(x.shape[2])
+        A, t = self._dev_f64(A, 9, "A"), self._dev_f64(t, 3, "t")
+        out = self._out_like(out, "color_apply", 3 * H * W)
+        if out is None:
+            out = torch.empty((1, 3, H, W), device=x.device, dtype=torch.float32)
+        self._stream()
+        self._chk(self._lib.wct_color_apply(self._ctx, x.data_ptr(), H, W, A.data_ptr(), t.data_ptr(), out.data_ptr()))
+        return out.view(1, 3, H, W)
+
+    @torch.no_grad()
+    def color_match(self, style: torch.Tensor, content: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The style image with its colours mapped onto the content's colour distribution (Gatys et al. 2017, section 5; the
+        reference's whiten_and_color on pixels): color_moments of both + color_solve + color_apply in one call (wct_color_match),
+        bit-identical to that chain.  `out` may be `style` itself."""
+        s, c = self._img(style), self._img(content)
+        Hs, Ws, H, W = int(s.shape[1]), int(s.shape[2]), int(c.shape[1]), int(c.shape[2])
+        out = self._out_like(out, "color_match", 3 * Hs * Ws)
+        if out is None:
+            out = torch.empty((1, 3, Hs, Ws), device=s.device, dtype=torch.float32)
+        self._stream()
+        self._chk(self._lib.wct_color_match(self._ctx, s.data_ptr(), Hs, Ws, c.data_ptr(), H, W, out.data_ptr()))
+        return out.view(1, 3, Hs, Ws)
+
+    @torch.no_grad()
+    def luma_merge(self, stylised: torch.Tensor, content: torch.Tensor, out: Optional[torch.Tensor] = None, u8: bool = False,
+                   round_mode: int = 0) -> torch.Tensor:
+        """The content's chroma with the stylised luminance: out_c = content_c + (Y(stylised) - Y(content)) over the top-left window
+        of the content that the result covers (wct_luma_merge).  u8=False: fp32 [1,3,Ho,Wo]; u8=True: uint8 [Ho,Wo,3] with the
+        conversion of to_u8(., round_mode) fused in, byte-identical to to_u8 of the fp32 result."""
+        s, c = self._img(stylised), self._img(content)
+        Ho, Wo, Hc, Wc = int(s.shape[1]), int(s.shape[2]), int(c.shape[1]), int(c.shape[2])
+        if Ho > Hc or Wo > Wc:
+            raise ValueError("luma_merge: the result (%d x %d) is larger than the content (%d x %d)" % (Ho, Wo, Hc, Wc))
+        out = self._out_like(out, "luma_merge", 3 * Ho * Wo, torch.uint8 if u8 else torch.float32)
+        if out is None:
+            out = torch.empty((Ho, Wo, 3), device=s.device, dtype=torch.uint8) if u8 else \
+                torch.empty((1, 3, Ho, Wo), device=s.device, dtype=torch.float32)
+        self._stream()
+        self._chk(self._lib.wct_luma_merge(self._ctx, s.data_ptr(), Ho, Wo, c.data_ptr(), Hc, Wc, None if u8 else out.data_ptr(),
+                                           out.data_ptr() if u8 else None, int(round_mode)))
+        return out.view(Ho, Wo, 3) if u8 else out.view(1, 3, Ho, Wo)
+
+    @torch.no_grad()
+    def stylize_color(self, contentImg: torch.Tensor, styleImg: torch.Tensor, mode: str, alpha: Optional[float] = None, num_run: int = 1,
+                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """stylize() with colour preservation, one library call (wct_stylize_color).  mode "match": the style is colour-matched to
+        the content once, before the cascade; "luma": the result keeps the content's chroma (luma_merge after the last run);
+        "match+luma": both.  Bit-identical to the composition of color_match / stylize / luma_merge; afterwards the prepared style
+        statistics are the MATCHED style's."""
+        if mode not in _lib.COLOR_MODES:
+            raise ValueError("stylize_color: mode must be one of %s, got %r" % (", ".join(repr(m) for m in _lib.COLOR_MODES), mode))
+        alpha = self.alpha if alpha is None else float(alpha)
+        c, s = self._img(contentImg), self._img(styleImg)
+        H, W, Hs, Ws = int(c.shape[1]), int(c.shape[2]), int(s.shape[1]), int(s.shape[2])
+        out = self._out_image(out, H, W)
+        ho, wo = c_int(), c_int()
+        self._stream()
+        self._chk(self._lib.wct_stylize_color(self._ctx, c.data_ptr(), H, W, s.data_ptr(), Hs, Ws, alpha, int(num_run), _lib.COLOR_MODES[mode],
+                                              out.data_ptr(), byref(ho), byref(wo)))
+        self._style_keep = s      # the matching reads it asynchronously
+        return out.view(-1)[: 3 * ho.value * wo.value].view(1, 3, ho.value, wo.value)
+
     # ------------------------------------------------------------------ spatial control (regions)
     def _labels(self, labels: torch.Tensor, h: int, w: int) -> torch.Tensor:
         if labels.dtype != torch.uint8 or tuple(labels.shape) != (h, w):

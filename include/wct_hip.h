@@ -462,6 +462,9 @@ int wct_resize_u8(wct_ctx* ctx, const uint8_t* src_hwc, int H, int W, uint8_t* d
 int wct_resize_u8_to_planar(wct_ctx* ctx, const uint8_t* src_hwc, int H, int W, float* planar, int oH, int oW);
 int wct_resize_u8_filter(wct_ctx* ctx, const uint8_t* src_hwc, int H, int W, uint8_t* dst_hwc, float* planar, int oH, int oW, int filter);
 
+/* Colour preservation -- the entries behind `--preserve_color match | luma`: colour moments, solve, apply, match, the luminance merge and
+ * the cascade with either control -- is declared in wct_hip_color.h, a header of its own that includes this one; libwct_hip.so exports both. */
+
 /* wct_reserve allocates, up front, every workspace buffer that wct_stylize, wct_stylize_prepared and wct_style_prepare(_levels) of
  * this content / style size touch, under the context's current mode switches: after it, those calls at this or any smaller size
  * allocate nothing (wct_debug_get "ws_allocs" does not move), and a reserve of a smaller size is a no-op.  wct_workspace_bytes is
