@@ -1271,6 +1271,7 @@ hipError_t launch_enc_head(const ConvDesc& d0, const ConvDesc& d1, const float* 
       if (e != hipSuccess) return e;
     }
     const int ntiles = a.tiles_x * a.tiles_y, grid = ntiles < G::PER_CU * num_cus() ? ntiles : G::PER_CU * num_cus();
+    note_launch_form('t', th, ntiles, grid);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(G::NT), G::lds, s, a);
     return hipGetLastError();
   };
@@ -1283,6 +1284,7 @@ hipError_t launch_enc_head(const ConvDesc& d0, const ConvDesc& d1, const float* 
   if (roles_env && !th_env && ((H + 15) / 16) * a.tiles_x >= 4 * num_cus()) {
     a.tiles_y = (H + 15) / 16;
     const int ntiles = a.tiles_x * a.tiles_y, grid = ntiles < num_cus() ? ntiles : num_cus();
+    note_launch_form('r', 16, ntiles, grid);
     auto gor = [&](auto kern, auto geo) -> hipError_t {
       using G = decltype(geo);
       hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::lds);
@@ -1326,6 +1328,7 @@ hipError_t launch_dec_tail(const ConvDesc& d0, const ConvDesc& d1, const float* 
       hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::lds);
       if (e != hipSuccess) return e;
       const int ntiles = a.tiles_x * a.tiles_y, grid = ntiles < per_cu * num_cus() ? ntiles : per_cu * num_cus();
+      note_launch_form('u', G::HROWS - 2, ntiles, grid);
       hipLaunchKernelGGL(kern, dim3(grid), dim3(G::NT), G::lds, s, a);
       return hipGetLastError();
     };
@@ -1344,6 +1347,7 @@ hipError_t launch_dec_tail(const ConvDesc& d0, const ConvDesc& d1, const float* 
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
     const int ntiles = a.tiles_x * a.tiles_y, grid = ntiles < per_cu * num_cus() ? ntiles : per_cu * num_cus();
+    note_launch_form('t', G::HROWS - 2, ntiles, grid);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(G::NT), lds, s, a);
     return hipGetLastError();
   };
@@ -1398,6 +1402,7 @@ hipError_t launch_conv3x3_f16(const ConvDesc& d, const float* in, float* out, in
   const size_t act_b = (size_t)4 * npp(8) * 16;
   if (d.cout_pad == 16) {
     a.taps = 10;
+    note_launch_form('t', 8, 0, 0);
     const size_t lds = act_b + (size_t)40 * 16 * 16;
     if (out3) return pool ? hipErrorInvalidValue : launch_k(conv3x3_f16_c16_kernel<false, true>, a, lds, 1, s);
     return pool ? launch_k(conv3x3_f16_c16_kernel<true, false>, a, lds, 1, s) : launch_k(conv3x3_f16_c16_kernel<false, false>, a, lds, 1, s);
@@ -1410,11 +1415,14 @@ hipError_t launch_conv3x3_f16(const ConvDesc& d, const float* in, float* out, in
     groups = d.cout_pad / 128; ct = 4;
   }
   // small maps (level 5's first decoder conv: 135 x 240 x 128 -> 72 tiles of 32 x 16 on 256 CUs): 32 x 8 tiles and cout groups of
-  // 64 instead -- four times the workgroups, the same arithmetic per output (bit-identical)
+  // 64 instead -- four times the workgroups, the same arithmetic per output (bit-identical: tests/test_geometry_gpu.py compares
+  // the two forms' digests under WCT_F16_SMALL=0 / 1)
   static const int small_env = [] { const char* e = wct_debug_env("WCT_F16_SMALL"); return e ? atoi(e) : 1; }();
+  bool small = false;
   if (ct == 4 && small_env && a.tiles_x * ((H + 15) / 16) * groups < num_cus()) {
-    ct = 2; groups = d.cout_pad / 64;
+    ct = 2; groups = d.cout_pad / 64; small = true;
   }
+  note_launch_form(small ? 's' : 't', ct == 4 ? 16 : 8, 0, 0);   // one workgroup per (tile, cout group): never more than one unit
   if (ct == 4) {  // 128 couts: 32 x 16 pixel tile, 8 waves (2 per SIMD), the 74 KB weight slab serves 512 pixels
     a.tiles_y = (H + 15) / 16;
     const size_t lds16 = (size_t)4 * npp(16) * 16 + (size_t)36 * 128 * 16;

@@ -310,7 +310,7 @@ __global__ __launch_bounds__(512) void conv3x3_sp_kernel(SpArgs a) {
 //   * job j issues the DMA of job j + 2 into the third stage, on its LAST taps, and the parked epilogue of the previous tile on its
 //     FIRST taps, so that at the top of job j + 1 `s_waitcnt vmcnt(5)` (the wave's five newest vector-memory operations = the DMA
 //     of job j + 2, issued unconditionally) waits for job j + 1's stage and for the stores, while a whole stage stays in flight.
-// Same tiles, same MFMA order, same epilogue as the kernel above: results are bit-identical (tests/test_hip_parity.py).
+// Same tiles, same MFMA order, same epilogue as the kernel above: results are bit-identical (tests/test_geometry_gpu.py, WCT_SP3=0 / 1).
 // (Also built and measured, not kept: the opposite order -- DMA on the first taps, the stores LAST and unconditional (lanes without an
 // output pixel writing to a sink), `vmcnt(5 + stores)` so that the stores stay in flight across the barrier as well.  4 % slower on the
 // same box, 0.705 against 0.678 ms per step for the family: it is the stage of loads in flight that pays, not the stores' latency.
@@ -682,12 +682,13 @@ __global__ __launch_bounds__(512) void conv3x3_sp_up_kernel(SpArgs a) {
 }
 
 template <typename K>
-hipError_t launch_sp(K k, const SpArgs& a, size_t lds, hipStream_t s, int threads) {
+hipError_t launch_sp(K k, const SpArgs& a, size_t lds, hipStream_t s, int threads, char form = 't') {
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) return e;
   // (tile, group) units per XCD queue x 8 queues, capped at one workgroup per CU; a multiple of 8 (workgroup b -> XCD b & 7)
   const int ntiles = a.tiles_x * a.tiles_y, want = 8 * ((ntiles + 7) / 8) * a.groups, cus = (num_cus() & ~7) > 8 ? (num_cus() & ~7) : 8;
   const int grid = want < cus ? want : cus;
+  note_launch_form(form, SPH, (long)ntiles * a.groups, grid);
   hipLaunchKernelGGL(k, dim3(grid), dim3(threads), lds, s, a);
   return hipGetLastError();
 }
@@ -738,7 +739,7 @@ hipError_t launch_conv3x3_sp(const ConvDesc& d, const void* in, void* out, int H
     a.tiles_x = (a.inW + FTW - 1) / FTW; a.tiles_y = (a.inH + SPH - 1) / SPH;
     a.groups = 2 * (d.cout_pad / 32);
     const size_t ldsu = (size_t)2 * (4 * SP_NPP + 32 * 32) * 16 + (size_t)d.cout_pad * sizeof(float);   // 114.8 KB
-    return f32 ? launch_sp(conv3x3_sp_up_kernel<true>, a, ldsu, s, 512) : launch_sp(conv3x3_sp_up_kernel<false>, a, ldsu, s, 512);
+    return f32 ? launch_sp(conv3x3_sp_up_kernel<true>, a, ldsu, s, 512, 'u') : launch_sp(conv3x3_sp_up_kernel<false>, a, ldsu, s, 512, 'u');
   }
   const int ct = (d.cout_pad % 64 == 0) ? 2 : 1;
   a.groups = d.cout_pad / (ct * 32);
@@ -746,8 +747,8 @@ hipError_t launch_conv3x3_sp(const ConvDesc& d, const void* in, void* out, int H
   static const int sp3_env = [] { const char* e = wct_debug_env("WCT_SP3"); return e ? atoi(e) : 1; }();
   if (sp3_env && d.cout_pad == 32 && d.cin_chunks <= 2) {
     const size_t lds3 = ((size_t)3 * 4 * SP_NPP + (size_t)d.cin_chunks * 36 * 32) * 16 + (size_t)d.cout_pad * sizeof(float);
-    if (pool) return f32 ? launch_sp(conv3x3_sp3_kernel<true, true>, a, lds3, s, 512) : launch_sp(conv3x3_sp3_kernel<true, false>, a, lds3, s, 512);
-    return f32 ? launch_sp(conv3x3_sp3_kernel<false, true>, a, lds3, s, 512) : launch_sp(conv3x3_sp3_kernel<false, false>, a, lds3, s, 512);
+    if (pool) return f32 ? launch_sp(conv3x3_sp3_kernel<true, true>, a, lds3, s, 512, '3') : launch_sp(conv3x3_sp3_kernel<true, false>, a, lds3, s, 512, '3');
+    return f32 ? launch_sp(conv3x3_sp3_kernel<false, true>, a, lds3, s, 512, '3') : launch_sp(conv3x3_sp3_kernel<false, false>, a, lds3, s, 512, '3');
   }
   const size_t lds = (size_t)2 * (4 * SP_NPP + 36 * ct * 32) * 16 + (size_t)d.cout_pad * sizeof(float);
 #define WCT_SP_CASE(CTV, GV)                                                                                          \

@@ -456,11 +456,12 @@ hipError_t launch_l1_decode(const ConvDesc& e, const ConvDesc& dec0, const float
     hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::lds);
     if (err != hipSuccess) return err;
     const int ntiles = a.tiles_x * a.tiles_y, grid = ntiles < per_cu * num_cus() ? ntiles : per_cu * num_cus();
+    note_launch_form('t', th, ntiles, grid);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(G::NT), G::lds, s, a);
     return hipGetLastError();
   };
   // 32 x 16 tiles (less halo recompute, one workgroup of eight waves per CU) once they still fill the chip, else 32 x 8 tiles, two workgroups of
-  // four waves per CU; results do not depend on the tile shape.  Measured at 4K (round 6, same box, profiles/r06_l1_decode_ab.txt): 32 x 16 one
+  // four waves per CU; results do not depend on the tile shape (tests/test_geometry_gpu.py, WCT_L1DEC_TH).  Measured at 4K (round 6, same box, profiles/r06_l1_decode_ab.txt): 32 x 16 one
   // per CU 0.229 ms, 32 x 8 two per CU 0.246, 32 x 8 one per CU 0.374 (round 5's kernel, weights in LDS: 0.255-0.262).  WCT_L1DEC_TH forces one.
   const bool tall = th_env ? th_env == 16 : ((H + 15) / 16) * a.tiles_x >= 2 * num_cus();
   return tall ? go(l1_decode_kernel<16>, L1DecGeo<16>{}, 16, 1) : go(l1_decode_kernel<8>, L1DecGeo<8>{}, 8, 2);

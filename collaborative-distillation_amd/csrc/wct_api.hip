@@ -62,6 +62,8 @@ struct ProfRec {
 
 }  // namespace
 
+__thread LaunchForm wct_launch_form = {0, 0, false};   // wct_common.h
+
 // An in-order execution lane: a stream plus the scratch only that stream touches.  `main` runs on the caller's
 // stream (content side, assembly, decode); `side` is a context-owned stream on which the style side (encode,
 // moments, eigen-decomposition -- independent of the content) runs ahead and overlaps the content side.
@@ -144,6 +146,7 @@ struct wct_ctx {
   DevBuf shIn, shOut, shNext, shEdge, shStyle, shStats, shMb;
   // profiling
   bool prof = false;
+  bool prof_forms = false;   // debug key "prof_forms": profile names carry the launcher's chosen form (ProfScope)
   std::vector<ProfRec> recs;
   std::map<std::string, wct_prof_entry> prof_acc;
   // spatial control (wct_stylize_regions, wct_moments_labeled, wct_apply_labeled): K style slots per level (cov_s^(1/2), mu_s), the
@@ -307,12 +310,19 @@ struct ProfScope {
   ProfScope(wct_ctx* c, hipStream_t stream, const char* name, double flops, double bytes) : ctx(c), st(stream), on(c->prof) {
     if (!on) return;
     r.name = name; r.flops = flops; r.bytes = bytes; r.side = stream == c->side.stream;
+    wct_launch_form = LaunchForm{0, 0, false};
     (void)hipEventCreate(&r.e0); (void)hipEventCreate(&r.e1);
     (void)hipEventRecord(r.e0, st);
   }
   ~ProfScope() {
     if (!on) return;
     (void)hipEventRecord(r.e1, st);
+    // debug key "prof_forms": what the size-selected launcher inside this scope chose, e.g. "dec_tail_fused<16-16-3>#u16m"
+    if (ctx->prof_forms && wct_launch_form.form) {
+      char sfx[16];
+      snprintf(sfx, sizeof sfx, "#%c%d%s", wct_launch_form.form, wct_launch_form.tile_h, wct_launch_form.multi ? "m" : "");
+      r.name += sfx;
+    }
     ctx->recs.push_back(r);
   }
 };
@@ -1198,6 +1208,7 @@ int wct_debug_set(wct_ctx* ctx, const char* key, double value) {
   else if (!strcmp(key, "fastfold")) ctx->fastfold = v;
   else if (!strcmp(key, "interleave")) ctx->interleave = v;
   else if (!strcmp(key, "foldgemm")) ctx->foldgemm = v;
+  else if (!strcmp(key, "prof_forms")) ctx->prof_forms = v;
   else if (!strcmp(key, "nscoop")) ctx->nscoop = (int)value;      // 0: multi-launch, 1: single launch, 2: single launch with an injected placement fault
   else if (!strcmp(key, "mom32")) ctx->mom32 = (int)value;       // 0 / 1 / 2, see wct_ctx
   else if (!strcmp(key, "in3wide")) ctx->in3wide = (int)value;   // 2 / 1 / 0, see wct_ctx
@@ -1238,7 +1249,7 @@ int wct_debug_set(wct_ctx* ctx, const char* key, double value) {
     ctx->side.stream = ns;
     return WCT_OK;
   }
-  else return fail(ctx, WCT_ERR_INVALID, "debug_set: unknown key '%s' (fuse, sp, l1fuse, u8fuse, upconv, fastfold, interleave, foldgemm, nscoop, in3wide, mom32, eig_skip, side_priority, poison)", key);
+  else return fail(ctx, WCT_ERR_INVALID, "debug_set: unknown key '%s' (fuse, sp, l1fuse, u8fuse, upconv, fastfold, interleave, foldgemm, nscoop, in3wide, mom32, eig_skip, side_priority, poison, prof_forms)", key);
   HIPCHK(ctx, hipStreamSynchronize(ctx->side.stream));
   return WCT_OK;
 }

@@ -18,6 +18,18 @@ static inline const char* wct_debug_env(const char* name) {
   return getenv(name);
 }
 
+// What a size-selected launcher chose for its last launch on this host thread (launch_enc_head, launch_dec_tail, launch_l1_decode,
+// launch_conv3x3_f16, launch_conv3x3_sp).  The launchers are free functions without a context, so they leave the choice here and
+// wct_api.hip's ProfScope appends it to the profile record's name as "#<form><tile_h>[m]" when wct_debug_set("prof_forms", 1) is on
+// (tests/test_geometry_gpu.py).  form: 'r' two-role head, 't' plain nine-tap tiles, 'u' upsample (2x2 per parity) form, 's' small-map
+// form, '3' three-stage persistent kernel; 0 = the launcher has a single form and says nothing.  multi: the grid is smaller than
+// tiles x cout groups, so some workgroup walks more than one unit.  Defined in wct_api.hip; not part of the ABI.
+struct LaunchForm { char form; int tile_h; bool multi; };
+extern __thread LaunchForm wct_launch_form __attribute__((visibility("hidden")));
+static inline void note_launch_form(char form, int tile_h, long units, long grid) {
+  wct_launch_form.form = form; wct_launch_form.tile_h = tile_h; wct_launch_form.multi = units > grid;
+}
+
 // The context's saturation counter (wct_api.hip sat_dev): +1 per thread (or wave) that clamped an activation, SATURATING -- the
 // thread that wraps the 32-bit counter sees old == 0xffffffff itself and pins it at 2^31 (so does every add above it).
 __device__ __forceinline__ void sat_raise(unsigned* counter) {

@@ -113,6 +113,11 @@ int wct_range_flag_f64(wct_ctx* ctx, double* flag_dev);
  * unless the environment variable WCT_DEBUG is set; so is "shard_emulate" (100 * ranks + rank: a context holding a ONE-rank communicator runs
  * wct_stylize_sharded with the geometry of one rank of a larger job, its peers being itself -- what one rank of the job executes, with
  * other numbers; 0: off).  Environment variables WCT_* are honoured only when WCT_DEBUG is set.
+ * "prof_forms" (0 / 1, default 0) changes no result: with profiling enabled, the names of wct_profile_read() gain a suffix saying which
+ * kernel form the size-selected launchers chose, "#<form><tile height>[m]" -- form r = two-role head, t = plain tiles, u = upsample
+ * (2x2 per parity) form, s = small-map form, 3 = three-stage persistent kernel; m = the grid is smaller than tiles x cout groups, so a
+ * workgroup walks several units -- e.g. "dec_tail_fused<16-16-3>#u16m".  Launchers with one form add nothing; with the switch off the
+ * names are unchanged (tests/test_geometry_gpu.py).
  * "poison" (a byte 0..255, or -1 = off) is the test hook for "does a call read what an earlier call left in the workspace": it
  * synchronises both of the context's streams, fills every allocated SCRATCH buffer of the context with that byte and, until it is
  * turned off, every buffer the workspace allocates later as well (a grown buffer is a fresh allocation and usually zero pages).
