@@ -3,6 +3,7 @@
 // in the kernels of conv3x3.hip / moments.hip / solve.hip / misc.hip.
 #include "../../include/wct_hip.h"
 #include "../../include/wct_hip_color.h"
+#include "../../include/wct_hip_smooth.h"
 #include "wct_common.h"
 
 #include <cmath>
@@ -105,6 +106,9 @@ struct wct_ctx {
   // colour preservation (include/wct_hip_color.h): the matched style of wct_stylize_color (3 Hs Ws floats), its un-merged result (3 H W
   // floats), and [sum_s 3 | sumsq_s 9 | sum_c 3 | sumsq_c 9 | A 9 | t 3 | pad to 64 doubles | stage-1 partials of the colour moments]
   DevBuf colStyle, colOut, colWs;
+  // guided-filter smoothing (include/wct_hip_smooth.h): the window sums between the two directions of a box (21 fp64 planes) and the
+  // coefficients a, b between the two stages (12 fp32 planes); wct_stylize_smooth keeps its un-filtered result in colOut
+  DevBuf smSums, smAB;
   DevBuf l1img;       // level 1 fused: copy of the content image between wct_content_encode and wct_content_decode
   int cur_H = 0, cur_W = 0;
   int numpy_variant = 0;  // 1: `--numpy` semantics (util_wct.py:143): + I on the CONTENT covariance
@@ -172,7 +176,7 @@ struct wct_ctx {
   void each_buf(F&& f) {
     for (Lane* ln : {&main, &side})
       for (DevBuf* b : {&ln->actA, &ln->actB, &ln->wsMom, &ln->wsEig, &ln->sums}) f(*b, ln, true);
-    for (DevBuf* b : {&featS, &tmpT, &wsAsm, &small, &foldW, &foldW16, &eigC, &u8c, &u8s, &u8o, &rsz_tmp, &noise, &colStyle, &colOut, &colWs, &packed,
+    for (DevBuf* b : {&featS, &tmpT, &wsAsm, &small, &foldW, &foldW16, &eigC, &u8c, &u8s, &u8o, &rsz_tmp, &noise, &colStyle, &colOut, &colWs, &smSums, &smAB, &packed,
                       &shIn, &shOut, &shNext, &shEdge, &shStyle, &shStats, &shMb,
                       &regLab, &regHist, &regSums, &regMb, &regFeat, &wsRegMom, &wsRegApply,
                       &blendW, &blendStat, &wsBlendPool, &wsBlendApply})
@@ -2042,6 +2046,94 @@ int wct_stylize_color(wct_ctx* ctx, const float* content, int H, int W, const fl
   int ho = 0, wo = 0;
   if (int rc = stylize_impl(ctx, content, H, W, st, Hs, Ws, alpha, num_run, dst, &ho, &wo)) return rc;
   if (mode & WCT_COLOR_LUMA)
+    if (int rc = luma_merge_impl(ctx, dst, ho, wo, content, H, W, out, nullptr, 0)) return rc;
+  if (Ho) *Ho = ho;
+  if (Wo) *Wo = wo;
+  return WCT_OK;
+}
+
+// ---- guided-filter smoothing (include/wct_hip_smooth.h; kernels in smooth.hip) -------------------------------------------------------
+namespace {
+int smooth_bufs(wct_ctx* ctx, long npix) {
+  if (int rc = ensure(ctx, ctx->smSums, smooth_sums_bytes(npix))) return rc;
+  return ensure(ctx, ctx->smAB, smooth_ab_bytes(npix));
+}
+
+int guided_filter_impl(wct_ctx* ctx, const float* src, int Ho, int Wo, const float* guide, int Hg, int Wg, int radius, double eps, float* out_planar,
+                       uint8_t* out_hwc, int round_mode) {
+  const long npix = (long)Ho * Wo;
+  if (int rc = smooth_bufs(ctx, npix)) return rc;
+  ProfScope ps(ctx, ctx->main.stream, "guided_filter", 600.0 * npix, (24.0 + 168.0 * 2 + 48.0 * 2 + 96.0 * 2 + 12.0 + (out_planar ? 12.0 : 3.0)) * npix);
+  HIPCHK(ctx, launch_guided_filter(src, Ho, Wo, guide, Hg, Wg, radius, eps, out_planar, out_hwc, round_mode, reinterpret_cast<double*>(ctx->smSums.p),
+                                   ctx->smSums.cap, reinterpret_cast<float*>(ctx->smAB.p), ctx->smAB.cap, ctx->main.stream));
+  return WCT_OK;
+}
+
+// the refusals both entries share; `who` names the entry
+int smooth_check(wct_ctx* ctx, const char* who, int radius, double eps) {
+  if (radius < 1 || radius > WCT_SMOOTH_MAX_RADIUS)
+    return fail(ctx, WCT_ERR_INVALID, "%s: radius 1 .. %d expected, got %d", who, WCT_SMOOTH_MAX_RADIUS, radius);
+  if (!std::isfinite(eps) || !(eps > 0.0)) return fail(ctx, WCT_ERR_INVALID, "%s: eps must be finite and positive, got %g", who, eps);
+  return WCT_OK;
+}
+
+bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
+  const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+  return a0 < b0 + nb && b0 < a0 + na;
+}
+}  // namespace
+
+int wct_guided_filter(wct_ctx* ctx, const float* src, int Ho, int Wo, const float* guide, int Hg, int Wg, int radius, double eps, float* out_planar,
+                      uint8_t* out_hwc, int round_mode) {
+  if (!ctx) return WCT_ERR_INVALID;
+  WCT_GUARD(ctx);
+  if (!src || !guide) return fail(ctx, WCT_ERR_INVALID, "wct_guided_filter: NULL image");
+  if ((out_planar != nullptr) == (out_hwc != nullptr))
+    return fail(ctx, WCT_ERR_INVALID, "wct_guided_filter: exactly one of out_planar and out_hwc expected, got %s", out_planar ? "both" : "neither");
+  if (Ho < 1 || Wo < 1 || Ho > Hg || Wo > Wg)
+    return fail(ctx, WCT_ERR_INVALID, "wct_guided_filter: source %dx%d must be non-empty and no larger than the guide %dx%d", Ho, Wo, Hg, Wg);
+  if (int rc = smooth_check(ctx, "wct_guided_filter", radius, eps)) return rc;
+  if (round_mode != 0 && round_mode != 1) return fail(ctx, WCT_ERR_INVALID, "wct_guided_filter: round_mode 0 or 1 expected, got %d", round_mode);
+  const size_t out_bytes = (size_t)3 * Ho * Wo * (out_planar ? sizeof(float) : 1);
+  if (ranges_overlap(out_planar ? static_cast<const void*>(out_planar) : static_cast<const void*>(out_hwc), out_bytes, guide,
+                     (size_t)3 * Hg * Wg * sizeof(float)))
+    return fail(ctx, WCT_ERR_INVALID, "wct_guided_filter: the output overlaps the guide, which the last kernel still reads");
+  return guided_filter_impl(ctx, src, Ho, Wo, guide, Hg, Wg, radius, eps, out_planar, out_hwc, round_mode);
+}
+
+int wct_stylize_smooth(wct_ctx* ctx, const float* content, int H, int W, const float* style, int Hs, int Ws, float alpha, int num_run, int color_mode,
+                       int radius, double eps, float* out, int* Ho, int* Wo) {
+  if (!ctx) return WCT_ERR_INVALID;
+  WCT_GUARD(ctx);
+  if (!content || !style || !out || num_run < 1) return fail(ctx, WCT_ERR_INVALID, "wct_stylize_smooth: bad arguments (a NULL pointer, or num_run < 1)");
+  if (color_mode < 0 || color_mode > 3)
+    return fail(ctx, WCT_ERR_INVALID, "wct_stylize_smooth: color_mode %d is not 0, WCT_COLOR_MATCH (1), WCT_COLOR_LUMA (2) or both (3)", color_mode);
+  const bool match = color_mode & WCT_COLOR_MATCH, luma = color_mode & WCT_COLOR_LUMA;
+  if (H < 1 || W < 1 || Hs < 1 || Ws < 1 || (match && ((long)Hs * Ws < 2 || (long)H * W < 2)))
+    return fail(ctx, WCT_ERR_INVALID, "wct_stylize_smooth: bad shapes (content %dx%d, style %dx%d)", H, W, Hs, Ws);
+  if (match && ((long)Hs * Ws > color_moments_max_pixels() || (long)H * W > color_moments_max_pixels()))
+    return fail(ctx, WCT_ERR_INVALID, "wct_stylize_smooth: style %dx%d or content %dx%d exceeds the %ld pixels the summation contract covers", Hs, Ws, H, W,
+                color_moments_max_pixels());
+  if (int rc = smooth_check(ctx, "wct_stylize_smooth", radius, eps)) return rc;
+  if (ranges_overlap(out, (size_t)3 * H * W * sizeof(float), content, (size_t)3 * H * W * sizeof(float)))
+    return fail(ctx, WCT_ERR_INVALID, "wct_stylize_smooth: out overlaps the content, which is the filter's guide");
+  // every buffer first: a growing one synchronises, and nothing enqueued below may find its source moved
+  if (match)
+    if (int rc = ensure(ctx, ctx->colStyle, (size_t)3 * Hs * Ws * sizeof(float))) return rc;
+  if (luma)
+    if (int rc = ensure(ctx, ctx->colOut, (size_t)3 * H * W * sizeof(float))) return rc;
+  if (int rc = smooth_bufs(ctx, (long)H * W)) return rc;   // the result is no larger than the content
+  const float* st = style;
+  if (match) {
+    float* matched = reinterpret_cast<float*>(ctx->colStyle.p);
+    if (int rc = color_match_impl(ctx, style, Hs, Ws, content, H, W, matched)) return rc;
+    st = matched;
+  }
+  float* dst = luma ? reinterpret_cast<float*>(ctx->colOut.p) : out;
+  int ho = 0, wo = 0;
+  if (int rc = stylize_impl(ctx, content, H, W, st, Hs, Ws, alpha, num_run, dst, &ho, &wo)) return rc;
+  if (int rc = guided_filter_impl(ctx, dst, ho, wo, content, H, W, radius, eps, dst, nullptr, 0)) return rc;   // in place
+  if (luma)
     if (int rc = luma_merge_impl(ctx, dst, ho, wo, content, H, W, out, nullptr, 0)) return rc;
   if (Ho) *Ho = ho;
   if (Wo) *Wo = wo;

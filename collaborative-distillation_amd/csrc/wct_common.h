@@ -147,6 +147,14 @@ hipError_t launch_color_solve(double n_c, const double* sum_c, const double* sum
 hipError_t launch_color_apply(const float* in, long npix, const double* A, const double* t, float* out, hipStream_t s);
 hipError_t launch_luma_merge(const float* stylised, int Ho, int Wo, const float* content, int Hc, int Wc, float* out_planar, uint8_t* out_hwc,
                              int round_mode, hipStream_t s);
+// ---- guided-filter smoothing (smooth.hip; include/wct_hip_smooth.h): four launches on `s`; `sums` (21 fp64 planes of Ho Wo) and `ab` (12 fp32
+// planes) are the caller's scratch.  smooth_vseg / smooth_hseg: the rows / columns between two restarts of the running sums.
+int smooth_vseg(int r);
+int smooth_hseg();
+size_t smooth_sums_bytes(long npix);
+size_t smooth_ab_bytes(long npix);
+hipError_t launch_guided_filter(const float* src, int Ho, int Wo, const float* guide, int Hg, int Wg, int r, double eps, float* out_planar,
+                                uint8_t* out_hwc, int round_mode, double* sums, size_t sums_bytes, float* ab, size_t ab_bytes, hipStream_t s);
 // *dst = (double)*counter on the stream (wct_range_flag_f64: the saturation counter as a value a sharded run can all-reduce)
 hipError_t launch_counter_to_f64(const unsigned* counter, double* dst, hipStream_t s);
 // ---- image edge: transforms.Resize = Pillow's bilinear resampler, bit-exact (resize.hip)

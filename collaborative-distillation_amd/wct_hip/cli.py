@@ -28,6 +28,10 @@ GPU and only the uint8 result comes back.
 colours onto the content's colour distribution before the cascade (per pair: wct_stylize_color, no style-statistics cache), `luma`
 keeps the content's chroma and takes the stylised luminance (wct_luma_merge fused with the uint8 conversion; also behind --maskPath
 and --interp_styles / --weightPath).  The files carry _color=<mode> in their names.
+--smooth_radius R (not in the reference; the smoothing step of Li et al. 2018 as He et al.'s guided image filter) re-imposes the content's
+edge structure on the result: wct_guided_filter with the content tensor the cascade was given as colour guide, windows of radius R,
+regulariser --smooth_eps; it runs behind the cascade in every content-driven mode (before the luminance merge of --preserve_color luma),
+with the uint8 conversion fused into whichever kernel comes last.  The files carry _smooth=<R> in their names, after _color=<mode>.
 Decoding/encoding files needs Pillow on the host (the reference's own dependency); the GPU library is mandatory: there
 is no CPU fallback.
 """
@@ -91,6 +95,12 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--preserve_color", type=str, default=None, choices=["match", "luma"],
                    help="keep the content's colours: match = map the style's colours onto the content's colour distribution before "
                         "stylisation, luma = keep the content's chroma and take only the stylised luminance")
+    # not in the reference: guided-filter smoothing by the content image (include/wct_hip_smooth.h)
+    p.add_argument("--smooth_radius", type=int, default=0,
+                   help="radius in pixels of the guided filter that re-imposes the content's edges on the result (0 = off)")
+    p.add_argument("--smooth_eps", type=float, default=None,
+                   help="regulariser of --smooth_radius, relative to images in [0, 1] (default 1e-3); smaller follows the content's edges "
+                        "more tightly, larger smooths more")
     return p
 
 
@@ -128,9 +138,9 @@ def pair_name(content_file: str, style_file: str) -> str:
 def out_name(args, imname: str) -> str:
     """WCT.py:127 (str(1) for the integer default of --alpha, like '%s' % args.alpha there)."""
     color = getattr(args, "preserve_color", None)
-    if color:      # --preserve_color: runs with and without the flag never collide
-        return os.path.join(args.outf, "%s_mode=%s_alpha=%s_color=%s_%s" % (args.log_mark, args.mode, args.alpha, color, imname))
-    return os.path.join(args.outf, "%s_mode=%s_alpha=%s_%s" % (args.log_mark, args.mode, args.alpha, imname))
+    radius = getattr(args, "smooth_radius", 0)
+    marks = ("_color=%s" % color if color else "") + ("_smooth=%d" % radius if radius else "")   # runs with and without the flags never collide
+    return os.path.join(args.outf, "%s_mode=%s_alpha=%s%s_%s" % (args.log_mark, args.mode, args.alpha, marks, imname))
 
 
 def load_rgb_u8(path: str, size: int = 0):
@@ -249,10 +259,37 @@ def check_color_args(args) -> None:
                 raise ValueError("--preserve_color match does not mix with %s (several styles per content); use --preserve_color luma" % name)
 
 
+def check_smooth_args(args) -> None:
+    """--smooth_radius / --smooth_eps: the filter needs a content to guide by; --smooth_eps alone means nothing.  Fills in the default
+    regulariser."""
+    from .lib import SMOOTH_EPS, SMOOTH_MAX_RADIUS      # WCT_SMOOTH_EPS, WCT_SMOOTH_MAX_RADIUS (include/wct_hip_smooth.h)
+    radius, eps = getattr(args, "smooth_radius", 0), getattr(args, "smooth_eps", None)
+    if radius < 0:
+        raise ValueError("--smooth_radius: a radius >= 0 expected (0 = off), got %d" % radius)
+    if radius > SMOOTH_MAX_RADIUS:
+        raise ValueError("--smooth_radius: at most %d, got %d" % (SMOOTH_MAX_RADIUS, radius))
+    if radius == 0:
+        if eps is not None:
+            raise ValueError("--smooth_eps does nothing without --smooth_radius")
+        return
+    if args.synthesis:
+        raise ValueError("--smooth_radius does not mix with --synthesis: there is no content to guide the filter by")
+    if eps is None:
+        args.smooth_eps = SMOOTH_EPS
+    elif not (0.0 < eps < float("inf")):
+        raise ValueError("--smooth_eps: a finite positive value expected, got %r" % (eps,))
+
+
 def _finish_u8(wct, args, res, c_f32):
-    """The result as uint8 HWC on the device: save_image's conversion, with --preserve_color luma fused into the luminance merge
-    against the content tensor the cascade was given."""
-    if getattr(args, "preserve_color", None) == "luma":
+    """The result as uint8 HWC on the device: save_image's conversion, fused into whichever kernel comes last -- the guided filter of
+    --smooth_radius, then the luminance merge of --preserve_color luma, both against the content tensor the cascade was given."""
+    luma = getattr(args, "preserve_color", None) == "luma"
+    radius = getattr(args, "smooth_radius", 0)
+    if radius:
+        if not luma:
+            return wct.guided_filter(res, c_f32, radius, args.smooth_eps, u8=True, round_mode=args.round_mode)
+        res = wct.guided_filter(res, c_f32, radius, args.smooth_eps)
+    if luma:
         return wct.luma_merge(res, c_f32, u8=True, round_mode=args.round_mode)
     return wct.to_u8(res, args.round_mode)
 
@@ -714,6 +751,7 @@ def main(argv: Optional[List[str]] = None) -> int:
     check_interp_args(args)
     check_synthesis_args(args)
     check_color_args(args)
+    check_smooth_args(args)
     os.makedirs(args.outf, exist_ok=True)
     logprinter = LogPrinter(args.debug, os.path.join(args.outf, "log_%s_%s.txt" % (args.log_mark, args.mode)))
     logprinter(sorted(vars(args).items()))

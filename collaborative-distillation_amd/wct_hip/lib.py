@@ -38,6 +38,11 @@ COLOR_MATCH, COLOR_LUMA = 1, 2                                      # WCT_COLOR_
 COLOR_MODES = {"match": COLOR_MATCH, "luma": COLOR_LUMA, "match+luma": COLOR_MATCH | COLOR_LUMA}
 COLOR_EPS = 1e-5                                                    # WCT_COLOR_EPS
 
+# every symbol include/wct_hip_smooth.h declares (guided-filter smoothing by the content image); bound from the same libwct_hip.so
+SYMBOLS_SMOOTH = ["wct_guided_filter", "wct_stylize_smooth"]
+SMOOTH_MAX_RADIUS = 2048                                            # WCT_SMOOTH_MAX_RADIUS
+SMOOTH_EPS = 1e-3                                                   # WCT_SMOOTH_EPS
+
 
 class WctLayer(ctypes.Structure):
     _fields_ = [("cin", c_int), ("cout", c_int), ("pool_after", c_int), ("up_after", c_int),
@@ -164,6 +169,8 @@ def load() -> ctypes.CDLL:
     lib.wct_color_match.argtypes = [c_void_p, vp, c_int, c_int, vp, c_int, c_int, vp]
     lib.wct_luma_merge.argtypes = [c_void_p, vp, c_int, c_int, vp, c_int, c_int, vp, vp, c_int]
     lib.wct_stylize_color.argtypes = [c_void_p, vp, c_int, c_int, vp, c_int, c_int, c_float, c_int, c_int, vp, ip, ip]
+    lib.wct_guided_filter.argtypes = [c_void_p, vp, c_int, c_int, vp, c_int, c_int, c_int, c_double, vp, vp, c_int]
+    lib.wct_stylize_smooth.argtypes = [c_void_p, vp, c_int, c_int, vp, c_int, c_int, c_float, c_int, c_int, c_int, c_double, vp, ip, ip]
     lib.wct_workspace_bytes.argtypes = [c_void_p, c_int, c_int, c_int, c_int]
     lib.wct_workspace_bytes.restype = c_size_t
     lib.wct_reserve.argtypes = [c_void_p, c_int, c_int, c_int, c_int]

@@ -816,6 +816,57 @@ class WCT:
         self._style_keep = s      # the matching reads it asynchronously
         return out.view(-1)[: 3 * ho.value * wo.value].view(1, 3, ho.value, wo.value)
 
+    # ------------------------------------------------------------------ guided-filter smoothing (include/wct_hip_smooth.h)
+    @staticmethod
+    def _smooth_args(what: str, radius, eps) -> None:
+        if int(radius) != radius or not 1 <= int(radius) <= _lib.SMOOTH_MAX_RADIUS:
+            raise ValueError("%s: radius must be an integer in 1 .. %d, got %r" % (what, _lib.SMOOTH_MAX_RADIUS, radius))
+        if not (float(eps) > 0.0 and float(eps) < float("inf")):
+            raise ValueError("%s: eps must be finite and positive, got %r" % (what, eps))
+
+    @torch.no_grad()
+    def guided_filter(self, src: torch.Tensor, guide: torch.Tensor, radius: int, eps: float = _lib.SMOOTH_EPS, out: Optional[torch.Tensor] = None,
+                      u8: bool = False, round_mode: int = 0) -> torch.Tensor:
+        """He et al.'s guided image filter of `src` with the colour image `guide` (its top-left window that `src` covers): windows
+        of radius `radius` clipped to the image, regulariser `eps` relative to [0, 1] images, fp64 inside, not clamped
+        (wct_guided_filter).  u8=False: fp32 [1,3,Ho,Wo], `out` may be `src` itself; u8=True: uint8 [Ho,Wo,3] with the conversion
+        of to_u8(., round_mode) fused in, byte-identical to to_u8 of the fp32 result."""
+        s, g = self._img(src), self._img(guide)
+        Ho, Wo, Hg, Wg = int(s.shape[1]), int(s.shape[2]), int(g.shape[1]), int(g.shape[2])
+        if Ho > Hg or Wo > Wg:
+            raise ValueError("guided_filter: the source (%d x %d) is larger than the guide (%d x %d)" % (Ho, Wo, Hg, Wg))
+        self._smooth_args("guided_filter", radius, eps)
+        out = self._out_like(out, "guided_filter", 3 * Ho * Wo, torch.uint8 if u8 else torch.float32)
+        if out is None:
+            out = torch.empty((Ho, Wo, 3), device=s.device, dtype=torch.uint8) if u8 else \
+                torch.empty((1, 3, Ho, Wo), device=s.device, dtype=torch.float32)
+        self._stream()
+        self._chk(self._lib.wct_guided_filter(self._ctx, s.data_ptr(), Ho, Wo, g.data_ptr(), Hg, Wg, int(radius), float(eps),
+                                              None if u8 else out.data_ptr(), out.data_ptr() if u8 else None, int(round_mode)))
+        return out.view(Ho, Wo, 3) if u8 else out.view(1, 3, Ho, Wo)
+
+    @torch.no_grad()
+    def stylize_smooth(self, contentImg: torch.Tensor, styleImg: torch.Tensor, radius: int, eps: float = _lib.SMOOTH_EPS,
+                       color: Optional[str] = None, alpha: Optional[float] = None, num_run: int = 1,
+                       out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """stylize() followed by guided_filter() with the ORIGINAL content as guide, one library call (wct_stylize_smooth).  `color`
+        is None or a mode of stylize_color: "match" before the cascade, "luma" after the filter.  Bit-identical to the composition
+        of color_match / stylize / guided_filter / luma_merge; the prepared style statistics afterwards are those of the cascade it
+        wraps (the MATCHED style's with "match")."""
+        if color is not None and color not in _lib.COLOR_MODES:
+            raise ValueError("stylize_smooth: color must be None or one of %s, got %r" % (", ".join(repr(m) for m in _lib.COLOR_MODES), color))
+        self._smooth_args("stylize_smooth", radius, eps)
+        alpha = self.alpha if alpha is None else float(alpha)
+        c, s = self._img(contentImg), self._img(styleImg)
+        H, W, Hs, Ws = int(c.shape[1]), int(c.shape[2]), int(s.shape[1]), int(s.shape[2])
+        out = self._out_image(out, H, W)
+        ho, wo = c_int(), c_int()
+        self._stream()
+        self._chk(self._lib.wct_stylize_smooth(self._ctx, c.data_ptr(), H, W, s.data_ptr(), Hs, Ws, alpha, int(num_run),
+                                               _lib.COLOR_MODES[color] if color else 0, int(radius), float(eps), out.data_ptr(), byref(ho), byref(wo)))
+        self._style_keep = s      # the side stream (and the matching) read it asynchronously
+        return out.view(-1)[: 3 * ho.value * wo.value].view(1, 3, ho.value, wo.value)
+
     # ------------------------------------------------------------------ spatial control (regions)
     def _labels(self, labels: torch.Tensor, h: int, w: int) -> torch.Tensor:
         if labels.dtype != torch.uint8 or tuple(labels.shape) != (h, w):
