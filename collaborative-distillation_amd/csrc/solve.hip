@@ -1202,7 +1202,7 @@ hipError_t launch_fold_gemm(const double* rows, const float* bias, int cout, int
 
 hipError_t launch_eig(int C, double n, const double* sum, const double* sumsq, int inverse, double* res, int* info_dev,
                       void* ws, size_t ws_bytes, hipStream_t s, double diag_add, bool wide_model, int* ok_defer, int coop_xcd, unsigned* coop_state, int* coop_epoch,
-                      unsigned* coop_aborts, bool* coop_used_out) {
+                      unsigned* coop_aborts, bool* coop_used_out, int sched_maxit, double sched_guess) {
   if (C < 2 || (C & 1) || C > 512 || n < 2) return hipErrorInvalidValue;  // unbiased covariance needs n >= 2
   if (ws_bytes < eig_workspace_bytes(C)) return hipErrorOutOfMemory;
   const size_t cc = (size_t)C * C;
@@ -1229,14 +1229,18 @@ hipError_t launch_eig(int C, double n, const double* sum, const double* sumsq, i
   // iterations like the plain iteration in 26: 20 fewer always-enqueued stage launches per solve, 13/10 -> 11/11 executed
   // iterations on the 4K bench frame, 1.4 % of a cached-style frame (A/B on one box, tools/experiments/ns_guess.py).
   static const double guess_env = [] { const char* e = wct_debug_env("WCT_NS_GUESS"); return e ? atof(e) : -1.0; }();
-  const double guess = big || Cp <= 64 ? 0.0 : (guess_env >= 0. ? guess_env : 1e-5);
+  // sched_maxit > 0: the caller's schedule (the ot transform's B = S cov_c S, whose spectrum is the product of two covariances': wct_api.hip
+  // OT_SCHED); the deflated iteration needs none, it takes its 19-20 iterations whatever the matrix
+  const bool own = sched_maxit > 0 && !big;
+  if (own && (sched_maxit > COOP_MAXIT || !(sched_guess > 0.))) return hipErrorInvalidValue;
+  const double guess = big || Cp <= 64 ? 0.0 : (own ? sched_guess : guess_env >= 0. ? guess_env : 1e-5);
   // Cp <= 64 (round 4): the same scaled start inside the LDS kernel -- 16 / 18 / 15 plain iterations at levels 3 / 2 / 1 of the 4K bench
   // frame.  The schedule covers its first COOP_MAXIT steps; beyond them (a spectrum far below the guess) the plain iteration goes on
   // up to the unchanged budget NS_MAXIT, so a wrong guess still costs iterations only.
   static const double guess64_env = [] { const char* e = wct_debug_env("WCT_NS_GUESS64"); return e ? atof(e) : -1.0; }();
-  const double guess64 = guess64_env >= 0. ? guess64_env : 1e-5;
+  const double guess64 = own ? sched_guess : guess64_env >= 0. ? guess64_env : 1e-5;
   // C > 128 (original mode): the deflated, optimally scaled iteration takes 19-20 iterations whatever the matrix
-  const int maxit = maxit_env ? maxit_env : (C > 128 ? 24 : (guess > 0. ? 16 : NS_MAXIT));
+  const int maxit = own ? sched_maxit : maxit_env ? maxit_env : (C > 128 ? 24 : (guess > 0. ? 16 : NS_MAXIT));
   bool coop_used = false;
   if (Cp <= 64) {
     // one workgroup, iterates in LDS (see ns_lds_kernel)

@@ -4,6 +4,7 @@
 #include "../../include/wct_hip.h"
 #include "../../include/wct_hip_color.h"
 #include "../../include/wct_hip_smooth.h"
+#include "../../include/wct_hip_transform.h"
 #include "wct_common.h"
 
 #include <cmath>
@@ -112,6 +113,8 @@ struct wct_ctx {
   DevBuf l1img;       // level 1 fused: copy of the content image between wct_content_encode and wct_content_decode
   int cur_H = 0, cur_W = 0;
   int numpy_variant = 0;  // 1: `--numpy` semantics (util_wct.py:143): + I on the CONTENT covariance
+  int transform = 0;      // WCT_TRANSFORM_* (include/wct_hip_transform.h): which T the (M, b) of a level is made of (transform_mb)
+  DevBuf trBuf;           // ot: B = sym(S cov_c S) [C*C] | a product in flight [C*C] | zeros [C]  (ot_workspace_bytes)
   bool wide_model = false;  // a loaded encoder ends wider than 128 channels (--mode original): see launch_eig
   int l1fuse = 1;     // 1: level 1 of the 16x cascade without materialising relu1_1 (level1.hip)
   int sp = 1;         // 1: intermediate activations of the f16x3 path in SP16 (split at the producer, DMA-staged consumers)
@@ -176,7 +179,7 @@ struct wct_ctx {
   void each_buf(F&& f) {
     for (Lane* ln : {&main, &side})
       for (DevBuf* b : {&ln->actA, &ln->actB, &ln->wsMom, &ln->wsEig, &ln->sums}) f(*b, ln, true);
-    for (DevBuf* b : {&featS, &tmpT, &wsAsm, &small, &foldW, &foldW16, &eigC, &u8c, &u8s, &u8o, &rsz_tmp, &noise, &colStyle, &colOut, &colWs, &smSums, &smAB, &packed,
+    for (DevBuf* b : {&featS, &tmpT, &wsAsm, &trBuf, &small, &foldW, &foldW16, &eigC, &u8c, &u8s, &u8o, &rsz_tmp, &noise, &colStyle, &colOut, &colWs, &smSums, &smAB, &packed,
                       &shIn, &shOut, &shNext, &shEdge, &shStyle, &shStats, &shMb,
                       &regLab, &regHist, &regSums, &regMb, &regFeat, &wsRegMom, &wsRegApply,
                       &blendW, &blendStat, &wsBlendPool, &wsBlendApply})
@@ -779,8 +782,17 @@ bool coop_usable(wct_ctx* ctx, Lane& ln) {
   return !ln.coop_off;
 }
 
+// The iteration schedule for the inverse square root of the ot transform's B = sym(S cov_c S) (C <= 128; the deflated iteration of wider
+// matrices needs none).  B's spectrum is the product of two covariances': on the live block of real 16x features its condition is
+// 6.5e5 .. 8.8e8, where the covariance schedule (assumed lower bound 1e-5, 16 scaled / 26 plain steps) runs out of budget
+// and every solve would fall into the Jacobi net.  Scaled from an assumed lower bound 1e-10 the iteration takes 17-18 steps for any
+// condition up to 1e10 (numpy prototype); a wrong guess costs iterations, never correctness.  32 = the single-launch kernel's limit.
+constexpr int OT_MAXIT = 32;
+constexpr double OT_GUESS = 1e-10;
+
 // (n, sum, sumsq) of one feature map -> EigResult in `res` (covariance, Jacobi eigen-decomposition)
-int eig_impl(wct_ctx* ctx, Lane& ln, int C, double n, const double* sum, const double* sumsq, int inverse, DevBuf& res, int* info_dev) {
+// ot_sched: the matrix is the ot transform's B = S cov_c S entering as pseudo-moments (transform_mb) -- its own iteration schedule, never + I
+int eig_impl(wct_ctx* ctx, Lane& ln, int C, double n, const double* sum, const double* sumsq, int inverse, DevBuf& res, int* info_dev, bool ot_sched = false) {
   if (C < 2 || (C & 1) || C > 512) return fail(ctx, WCT_ERR_INVALID, "solve: C=%d must be even and <= 512", C);
   if (n < 2) return fail(ctx, WCT_ERR_INVALID, "solve: unbiased covariance needs >= 2 pixels (n=%g)", n);
   if (int rc = ensure(ctx, res, eig_result_bytes(C))) return rc;
@@ -795,8 +807,8 @@ int eig_impl(wct_ctx* ctx, Lane& ln, int C, double n, const double* sum, const d
   const bool coop_ok = ctx->nscoop && coop_usable(ctx, ln);
   bool coop_used = false;
   HIPCHK(ctx, launch_eig(C, n, sum, sumsq, inverse, reinterpret_cast<double*>(res.p), info_dev, ln.wsEig.p, ln.wsEig.cap, ln.stream,
-                         (inverse && ctx->numpy_variant) ? 1.0 : 0.0, ctx->wide_model, defer, coop_ok ? (ln.xcd | (ctx->nscoop == 2 ? 16 : 0)) : -1, ln.coop, &ln.coop_epoch,
-                         ctx->sat_dev + 2 + (&ln == &ctx->side ? 1 : 0), &coop_used));
+                         (inverse && ctx->numpy_variant && !ot_sched) ? 1.0 : 0.0, ctx->wide_model, defer, coop_ok ? (ln.xcd | (ctx->nscoop == 2 ? 16 : 0)) : -1, ln.coop, &ln.coop_epoch,
+                         ctx->sat_dev + 2 + (&ln == &ctx->side ? 1 : 0), &coop_used, ot_sched ? OT_MAXIT : 0, ot_sched ? OT_GUESS : -1.0));
   if (coop_used) ++ln.coop_solves;
   return WCT_OK;
 }
@@ -842,6 +854,43 @@ int assemble_impl(wct_ctx* ctx, int C, const DevBuf& eig_c, const DevBuf& eig_s,
   ProfScope ps(ctx, ctx->main.stream, "assemble_Mb", 0, 0);
   HIPCHK(ctx, launch_assemble(C, reinterpret_cast<const double*>(eig_c.p), reinterpret_cast<const double*>(eig_s.p), alpha, 1e-10,
                               M, b, ctx->wsAsm.p, ctx->wsAsm.cap, ctx->main.stream));
+  return WCT_OK;
+}
+
+// Content moments + a style EigResult (F = cov_s^(1/2), mu_s) -> (M, b) of the transform `mode` (include/wct_hip_transform.h), on the
+// main lane: THE place where a level's map is made.  info_dev[0] = how the content-side matrix function was solved.  style_ready (may
+// be null): the event behind which eig_s is complete; waited for as late as the mode allows -- wct solves the content side first.
+int transform_mb(wct_ctx* ctx, int mode, int C, double n, const double* sum, const double* sumsq, const DevBuf& eig_s, double alpha, double* M,
+                 double* b, int* info_dev, hipEvent_t style_ready) {
+  Lane& ln = ctx->main;
+  if (mode == WCT_TRANSFORM_WCT) {
+    if (int rc = eig_impl(ctx, ln, C, n, sum, sumsq, 1, ctx->eigC, info_dev)) return rc;
+    if (style_ready) HIPCHK(ctx, hipStreamWaitEvent(ln.stream, style_ready, 0));
+    return assemble_impl(ctx, C, ctx->eigC, eig_s, alpha, M, b);
+  }
+  if (mode != WCT_TRANSFORM_OT && mode != WCT_TRANSFORM_ADAIN) return fail(ctx, WCT_ERR_INVALID, "transform: mode %d outside 0..2", mode);
+  if (C < 2 || (C & 1) || C > 512) return fail(ctx, WCT_ERR_INVALID, "solve: C=%d must be even and <= 512", C);
+  if (n < 2) return fail(ctx, WCT_ERR_INVALID, "solve: unbiased covariance needs >= 2 pixels (n=%g)", n);
+  if (style_ready) HIPCHK(ctx, hipStreamWaitEvent(ln.stream, style_ready, 0));
+  const size_t cc = (size_t)C * C;
+  const double* es = reinterpret_cast<const double*>(eig_s.p);
+  const double *S = es + eig_result_F_offset(C), *mu_s = es + cc + C;
+  if (mode == WCT_TRANSFORM_ADAIN) {
+    ProfScope ps(ctx, ln.stream, "adain_assemble", 0, 0);
+    HIPCHK(ctx, launch_adain_assemble(C, alpha, WCT_ADAIN_EPS, S, mu_s, n, sum, sumsq, M, b, info_dev, ln.stream));
+    return WCT_OK;
+  }
+  if (int rc = ensure(ctx, ctx->trBuf, ot_workspace_bytes(C))) return rc;
+  double* B = reinterpret_cast<double*>(ctx->trBuf.p);
+  double *tmp = B + cc, *zeros = tmp + cc;
+  {
+    ProfScope ps(ctx, ln.stream, "ot_sandwich", 8.0 * C * cc, 0);
+    HIPCHK(ctx, launch_ot_sandwich(C, n, sum, sumsq, S, B, zeros, tmp, ln.stream));
+  }
+  // B^(-1/2) into eigC's F: the pseudo-moments n = 2, sum = 0, sumsq = B give cov = (B - 2 * 0 * 0) / (2 - 1) = B exactly
+  if (int rc = eig_impl(ctx, ln, C, 2.0, zeros, B, 1, ctx->eigC, info_dev, true)) return rc;
+  ProfScope ps(ctx, ln.stream, "ot_assemble", 4.0 * C * cc, 0);
+  HIPCHK(ctx, launch_ot_assemble(C, alpha, S, mu_s, reinterpret_cast<const double*>(ctx->eigC.p) + eig_result_F_offset(C), n, sum, tmp, M, b, ln.stream));
   return WCT_OK;
 }
 
@@ -1033,15 +1082,15 @@ int content_side(wct_ctx* ctx, int level, const float* content, int H, int W, fl
     if (int rc = encode_impl(ctx, ln, level, content, H, W, fC, nullptr, nullptr)) return rc;
     if (int rc = moments_impl(ctx, ln, fC, C, h, w, 0, w, sv.sum, sv.sumsq)) return rc;
   }
-  if (int rc = eig_impl(ctx, ln, C, (double)h * w, sv.sum, sv.sumsq, 1, ctx->eigC, sv.info)) return rc;
   // csF = wct.transform(cF, sF, csF, alpha)                  (WCT.py:104) -- as an affine map
-  HIPCHK(ctx, hipStreamWaitEvent(ln.stream, ctx->ev_style[level], 0));
   // Img = decoder(csF)                                       (WCT.py:105) -- M, b folded into the first conv
   ConvDesc first;
-  if (ctx->conv_mode == 1 && ctx->fold_ready[level] && fast_fold_level(ctx, level)) {
+  if (ctx->transform == WCT_TRANSFORM_WCT && ctx->conv_mode == 1 && ctx->fold_ready[level] && fast_fold_level(ctx, level)) {
+    if (int rc = eig_impl(ctx, ln, C, (double)h * w, sv.sum, sv.sumsq, 1, ctx->eigC, sv.info)) return rc;
+    HIPCHK(ctx, hipStreamWaitEvent(ln.stream, ctx->ev_style[level], 0));
     if (int rc = fold_fast_impl(ctx, level, alpha, first)) return rc;      // straight from cov_c^(-1/2): no T, M, b on the critical path
   } else {
-    if (int rc = assemble_impl(ctx, C, ctx->eigC, ctx->eigS[level], alpha, M, b)) return rc;
+    if (int rc = transform_mb(ctx, ctx->transform, C, (double)h * w, sv.sum, sv.sumsq, ctx->eigS[level], alpha, M, b, sv.info, ctx->ev_style[level])) return rc;
     if (int rc = fold_impl(ctx, level, M, b, first)) return rc;
   }
   if (l1) {
@@ -1469,9 +1518,9 @@ int wct_solve(wct_ctx* ctx, int C, double n_c, const double* sum_c, const double
   if (!sum_c || !sumsq_c || !sum_s || !sumsq_s || !M || !b) return fail(ctx, WCT_ERR_INVALID, "solve: NULL pointer");
   SumsView sv;
   if (int rc = sums_view(ctx, ctx->main, sv)) return rc;
-  if (int rc = eig_impl(ctx, ctx->main, C, n_c, sum_c, sumsq_c, 1, ctx->eigC, sv.info)) return rc;
+  // the style side first: ot and adain read cov_s^(1/2) while they work on the content side (the order does not touch a result)
   if (int rc = eig_impl(ctx, ctx->main, C, n_s, sum_s, sumsq_s, 0, ctx->eigS[0], sv.info + 1)) return rc;
-  if (int rc = assemble_impl(ctx, C, ctx->eigC, ctx->eigS[0], alpha, M, b)) return rc;
+  if (int rc = transform_mb(ctx, ctx->transform, C, n_c, sum_c, sumsq_c, ctx->eigS[0], alpha, M, b, sv.info, nullptr)) return rc;
   if (info) {
     HIPCHK(ctx, hipMemcpyAsync(info, sv.info, 2 * sizeof(int), hipMemcpyDeviceToHost, ctx->main.stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->main.stream));
@@ -1524,11 +1573,11 @@ int wct_transform(wct_ctx* ctx, const float* cF, int C, int h, int w, const floa
     c = reinterpret_cast<float*>(ctx->featC.p);
     s = reinterpret_cast<float*>(ctx->featS.p);
   }
-  if (int rc = moments_impl(ctx, ln, c, C, h, w, 0, w, sv.sum, sv.sumsq)) return rc;
-  if (int rc = eig_impl(ctx, ln, C, (double)h * w, sv.sum, sv.sumsq, 1, ctx->eigC, sv.info)) return rc;
+  // the style side first: its moments share the lane's buffer with the content's, which ot and adain read next to cov_s^(1/2)
   if (int rc = moments_impl(ctx, ln, s, C, hs, ws, 0, ws, sv.sum, sv.sumsq)) return rc;
   if (int rc = eig_impl(ctx, ln, C, (double)hs * ws, sv.sum, sv.sumsq, 0, ctx->eigS[0], sv.info + 1)) return rc;
-  if (int rc = assemble_impl(ctx, C, ctx->eigC, ctx->eigS[0], alpha, M, b)) return rc;
+  if (int rc = moments_impl(ctx, ln, c, C, h, w, 0, w, sv.sum, sv.sumsq)) return rc;
+  if (int rc = transform_mb(ctx, ctx->transform, C, (double)h * w, sv.sum, sv.sumsq, ctx->eigS[0], alpha, M, b, sv.info, nullptr)) return rc;
   return wct_apply(ctx, cF, C, h, w, layout, M, b, out);
 }
 
@@ -1655,9 +1704,7 @@ int wct_content_solve(wct_ctx* ctx, int level, double n_c, const double* sum_c, 
   const int C = me.layers.back().d.cout;
   SumsView sv;
   if (int rc = sums_view(ctx, ctx->main, sv)) return rc;
-  if (int rc = eig_impl(ctx, ctx->main, C, n_c, sum_c, sumsq_c, 1, ctx->eigC, sv.info)) return rc;
-  HIPCHK(ctx, hipStreamWaitEvent(ctx->main.stream, ctx->ev_style[level], 0));
-  return assemble_impl(ctx, C, ctx->eigC, ctx->eigS[level], alpha, M, b);
+  return transform_mb(ctx, ctx->transform, C, n_c, sum_c, sumsq_c, ctx->eigS[level], alpha, M, b, sv.info, ctx->ev_style[level]);
 }
 
 int wct_content_decode(wct_ctx* ctx, int level, const double* M, const double* b, float* out, int* Ho, int* Wo) {
@@ -2316,6 +2363,7 @@ void workspace_plan(wct_ctx* ctx, int H, int W, int Hs, int Ws, std::vector<WsNe
   need.push_back({&ctx->tmpT, (size_t)3 * H * W * sizeof(float)});
   need.push_back({&ctx->eigC, eig_result_bytes(cmax)});
   need.push_back({&ctx->wsAsm, assemble_workspace_bytes(cmax)});
+  if (ctx->transform == WCT_TRANSFORM_OT) need.push_back({&ctx->trBuf, ot_workspace_bytes(cmax)});
   for (Lane* ln : {&ctx->main, &ctx->side}) {
     need.push_back({&ln->wsEig, eig_workspace_bytes(cmax)});
     need.push_back({&ln->sums, SUMS_BYTES});
@@ -2354,7 +2402,53 @@ int wct_reserve(wct_ctx* ctx, int H, int W, int Hs, int Ws) {
 int wct_set_numpy_variant(wct_ctx* ctx, int on) {
   if (!ctx) return WCT_ERR_INVALID;
   WCT_GUARD(ctx);
+  if (on && ctx->transform != WCT_TRANSFORM_WCT) return fail(ctx, WCT_ERR_INVALID, "set_numpy_variant: the + I variant is defined for the wct transform only (wct_set_transform)");
   ctx->numpy_variant = on ? 1 : 0;
+  return WCT_OK;
+}
+
+int wct_set_transform(wct_ctx* ctx, int mode) {
+  if (!ctx) return WCT_ERR_INVALID;
+  WCT_GUARD(ctx);
+  if (mode != WCT_TRANSFORM_WCT && mode != WCT_TRANSFORM_OT && mode != WCT_TRANSFORM_ADAIN) return fail(ctx, WCT_ERR_INVALID, "set_transform: mode %d outside 0..2", mode);
+  if (mode != WCT_TRANSFORM_WCT && ctx->numpy_variant) return fail(ctx, WCT_ERR_INVALID, "set_transform: the numpy variant (+ I on cov_c) is defined for the wct transform only");
+  ctx->transform = mode;
+  return WCT_OK;
+}
+
+int wct_get_transform(const wct_ctx* ctx, int* mode) {
+  if (!ctx || !mode) return WCT_ERR_INVALID;
+  *mode = ctx->transform;
+  return WCT_OK;
+}
+
+int wct_transform_solve(wct_ctx* ctx, int mode, int C, double n_c, const double* sum_c, const double* sumsq_c, const double* style_stats, double alpha,
+                        double* M, double* b, int* info) {
+  if (!ctx) return WCT_ERR_INVALID;
+  WCT_GUARD(ctx);
+  if (!sum_c || !sumsq_c || !style_stats || !M || !b) return fail(ctx, WCT_ERR_INVALID, "transform_solve: NULL pointer");
+  if (mode != WCT_TRANSFORM_WCT && mode != WCT_TRANSFORM_OT && mode != WCT_TRANSFORM_ADAIN) return fail(ctx, WCT_ERR_INVALID, "transform_solve: mode %d outside 0..2", mode);
+  if (C < 2 || (C & 1) || C > 512) return fail(ctx, WCT_ERR_INVALID, "transform_solve: C=%d must be even and <= 512", C);
+  if (!(n_c >= 2)) return fail(ctx, WCT_ERR_INVALID, "transform_solve: unbiased covariance needs >= 2 pixels (n=%g)", n_c);
+  SumsView sv;
+  if (int rc = sums_view(ctx, ctx->main, sv)) return rc;
+  hipStream_t st = ctx->main.stream;
+  // the slot as an EigResult in eigS[0] (wct_solve's style buffer; no level uses it)
+  const size_t cc = (size_t)C * C;
+  if (int rc = ensure(ctx, ctx->eigS[0], eig_result_bytes(C))) return rc;
+  double* es = reinterpret_cast<double*>(ctx->eigS[0].p);
+  HIPCHK(ctx, hipMemcpyAsync(es + eig_result_F_offset(C), style_stats, cc * sizeof(double), hipMemcpyDeviceToDevice, st));
+  HIPCHK(ctx, hipMemcpyAsync(es + cc + C, style_stats + cc, (size_t)C * sizeof(double), hipMemcpyDeviceToDevice, st));
+  HIPCHK(ctx, hipMemsetAsync(sv.info, 0, 2 * sizeof(int), st));
+  const int numpy = ctx->numpy_variant;
+  ctx->numpy_variant = 0;     // mode-explicit: T as the header defines it
+  const int rc = transform_mb(ctx, mode, C, n_c, sum_c, sumsq_c, ctx->eigS[0], alpha, M, b, sv.info, nullptr);
+  ctx->numpy_variant = numpy;
+  if (rc) return rc;
+  if (info) {
+    HIPCHK(ctx, hipMemcpyAsync(info, sv.info, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+  }
   return WCT_OK;
 }
 
@@ -2541,6 +2635,7 @@ int wct_stylize_regions(wct_ctx* ctx, const float* content, int H, int W, const 
                         const int* Hs, const int* Ws, const float* alpha, int num_run, float* out, int* Ho, int* Wo) {
   if (!ctx) return WCT_ERR_INVALID;
   WCT_GUARD(ctx);
+  if (ctx->transform != WCT_TRANSFORM_WCT) return fail(ctx, WCT_ERR_INVALID, "stylize_regions: defined for the wct transform only (wct_set_transform)");
   if (!content || !labels || !styles || !Hs || !Ws || !alpha || !out || num_run < 1) return fail(ctx, WCT_ERR_INVALID, "stylize_regions: bad arguments");
   if (K < 1 || K > REG_MAX) return fail(ctx, WCT_ERR_INVALID, "stylize_regions: K=%d outside [1, %d]", K, REG_MAX);
   for (int k = 0; k < K; ++k) {
@@ -2828,6 +2923,7 @@ int wct_stylize_blend(wct_ctx* ctx, const float* content, int H, int W, const fl
                       const int* Ws, const float* alpha, int num_run, float* out, int* Ho, int* Wo) {
   if (!ctx) return WCT_ERR_INVALID;
   WCT_GUARD(ctx);
+  if (ctx->transform != WCT_TRANSFORM_WCT) return fail(ctx, WCT_ERR_INVALID, "stylize_blend: defined for the wct transform only (wct_set_transform)");
   if (!weights || !alpha) return fail(ctx, WCT_ERR_INVALID, "stylize_blend: bad arguments");
   if (int rc = multi_style_args(ctx, "stylize_blend", content, H, W, K, styles, Hs, Ws, num_run, out)) return rc;
   for (int k = 0; k < K; ++k)

@@ -196,12 +196,27 @@ size_t assemble_workspace_bytes(int C);
 bool eig_is_big(int C, bool wide_model);
 hipError_t launch_eig(int C, double n, const double* sum, const double* sumsq, int inverse, double* res, int* info_dev,
                       void* workspace, size_t workspace_bytes, hipStream_t s, double diag_add = 0.0, bool wide_model = false,
-                      int* ok_defer = nullptr, int coop_xcd = -1, unsigned* coop_state = nullptr, int* coop_epoch = nullptr, unsigned* coop_aborts = nullptr, bool* coop_used_out = nullptr);
+                      int* ok_defer = nullptr, int coop_xcd = -1, unsigned* coop_state = nullptr, int* coop_epoch = nullptr, unsigned* coop_aborts = nullptr, bool* coop_used_out = nullptr,
+                      int sched_maxit = 0, double sched_guess = -1.0);
 //   coop_xcd (0..7, or -1: off) + coop_state (32 device bytes of the calling lane, zero at first use) + coop_epoch (the lane's
 //   HOST counter of such solves, advanced here): the 128-channel levels of --mode 16x as ONE launch on that XCD (solve.hip
 //   ns_coop128_kernel); lanes that may solve at the same time are given different XCDs
+//   sched_maxit > 0 (C <= 128 without deflation only; <= 32): the caller's own iteration budget and assumed lower spectral bound
+//   sched_guess of the scaled iteration instead of the defaults chosen for covariances (the ot transform's B = S cov_c S: transform.hip)
 hipError_t launch_assemble(int C, const double* eig_c, const double* eig_s, double alpha, double rel_thresh,
                            double* M, double* b, void* workspace, size_t workspace_bytes, hipStream_t s);
+
+// ---- the ot / adain transforms' C x C part (transform.hip; include/wct_hip_transform.h).  S, mu_s: the style slot (cov_s^(1/2), mean)
+//   launch_ot_sandwich  B = sym(S cov_c S) from the raw content moments, zeros[0..C) = 0 (B then enters launch_eig as the pseudo-moments
+//                       n = 2, sum = zeros, sumsq = B); tmp: C*C doubles
+//   launch_ot_assemble  T = S Z S (Z = B^(-1/2)), M = alpha T + (1 - alpha) I, b = alpha (mu_s - T sum_c / n); tmp: C*C doubles
+//   launch_adain_assemble  T = diag(sqrt((SUM_k S_ik^2 + eps) / (cov_c_ii + eps))), the same M and b; *info_dev = 0
+size_t ot_workspace_bytes(int C);   // B | tmp | zeros
+hipError_t launch_ot_sandwich(int C, double n, const double* sum_c, const double* sumsq_c, const double* S, double* B, double* zeros, double* tmp, hipStream_t s);
+hipError_t launch_ot_assemble(int C, double alpha, const double* S, const double* mu_s, const double* Z, double n, const double* sum_c, double* tmp,
+                              double* M, double* b, hipStream_t s);
+hipError_t launch_adain_assemble(int C, double alpha, double eps, const double* S, const double* mu_s, double n, const double* sum_c, const double* sumsq_c,
+                                 double* M, double* b, int* info_dev, hipStream_t s);
 
 // ---- fold csF = M x + b into a decoder's first conv:  W' = W o M, b' = bias + W o b
 //      w_oihw: device [cout][cin][3][3] fp32 (original weights), out: packed weights + bias for ConvDesc

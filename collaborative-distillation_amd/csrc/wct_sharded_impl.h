@@ -390,7 +390,7 @@ int wct_stylize_sharded(wct_ctx* ctx, const float* content_ext, int H, int W_tot
     // WCT_SHARD_FAST_FOLD: the single-GPU cascade's fold (content_side): (W cov_s^1/2) from the style lane times cov_c^-1/2 from the content solve straight
     // into the decoder's first conv -- no T, M, b and no assemble launch on the critical path; where the decoder allows it (cin <= 128, f16x3 mode) and
     // every rank folds for itself.  fp32 round-off from the (M, b) form below (tests/test_hip_parity.py test_fast_fold_matches_the_map_based_fold).
-    const bool fast = (flags & WCT_SHARD_FAST_FOLD) && !j.bmap && ctx->conv_mode == 1 && ctx->fold_ready[level] && fast_fold_level(ctx, level);
+    const bool fast = (flags & WCT_SHARD_FAST_FOLD) && ctx->transform == WCT_TRANSFORM_WCT && !j.bmap && ctx->conv_mode == 1 && ctx->fold_ready[level] && fast_fold_level(ctx, level);
     if (fast) {
       SumsView sv;
       if (int rc = sums_view(ctx, ctx->main, sv)) return rc;

@@ -101,6 +101,11 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--smooth_eps", type=float, default=None,
                    help="regulariser of --smooth_radius, relative to images in [0, 1] (default 1e-3); smaller follows the content's edges "
                         "more tightly, larger smooths more")
+    # not in the reference: the choice of feature transform (include/wct_hip_transform.h)
+    p.add_argument("--transform", type=str, default="wct", choices=["wct", "ot", "adain"],
+                   help="feature transform of every level: wct = the reference's whitening and colouring, ot = the optimal-transport map "
+                        "between the two feature Gaussians (same target statistics, moves the content least), adain = per-channel "
+                        "mean / std matching")
     return p
 
 
@@ -139,8 +144,10 @@ def out_name(args, imname: str) -> str:
     """WCT.py:127 (str(1) for the integer default of --alpha, like '%s' % args.alpha there)."""
     color = getattr(args, "preserve_color", None)
     radius = getattr(args, "smooth_radius", 0)
+    transform = getattr(args, "transform", None) or "wct"
+    tmark = "_transform=%s" % transform if transform != "wct" else ""                          # directly after alpha; wct names are unchanged
     marks = ("_color=%s" % color if color else "") + ("_smooth=%d" % radius if radius else "")   # runs with and without the flags never collide
-    return os.path.join(args.outf, "%s_mode=%s_alpha=%s%s_%s" % (args.log_mark, args.mode, args.alpha, marks, imname))
+    return os.path.join(args.outf, "%s_mode=%s_alpha=%s%s%s_%s" % (args.log_mark, args.mode, args.alpha, tmark, marks, imname))
 
 
 def load_rgb_u8(path: str, size: int = 0):
@@ -278,6 +285,21 @@ def check_smooth_args(args) -> None:
         args.smooth_eps = SMOOTH_EPS
     elif not (0.0 < eps < float("inf")):
         raise ValueError("--smooth_eps: a finite positive value expected, got %r" % (eps,))
+
+
+def check_transform_args(args) -> None:
+    """--transform ot | adain: everything goes with them (--pipeline, the style cache, the fp32 fallback, --synthesis, --interp_weights,
+    --preserve_color, --smooth_radius) but the wct-only variants: --numpy (+ I on the content covariance) and the per-pixel K-slot
+    paths of --maskPath and --weightPath (weighted-moment normalisations)."""
+    from .lib import TRANSFORMS
+    transform = getattr(args, "transform", None) or "wct"
+    if transform not in TRANSFORMS:
+        raise ValueError("--transform: one of %s expected, got %r" % (", ".join(sorted(TRANSFORMS)), transform))
+    if transform == "wct":
+        return
+    for flag, name in ((args.numpy, "--numpy"), (args.maskPath is not None, "--maskPath"), (args.weightPath is not None, "--weightPath")):
+        if flag:
+            raise ValueError("--transform %s does not mix with %s (defined for the wct transform only)" % (transform, name))
 
 
 def _finish_u8(wct, args, res, c_f32):
@@ -752,6 +774,7 @@ def main(argv: Optional[List[str]] = None) -> int:
     check_synthesis_args(args)
     check_color_args(args)
     check_smooth_args(args)
+    check_transform_args(args)
     os.makedirs(args.outf, exist_ok=True)
     logprinter = LogPrinter(args.debug, os.path.join(args.outf, "log_%s_%s.txt" % (args.log_mark, args.mode)))
     logprinter(sorted(vars(args).items()))

@@ -43,6 +43,12 @@ SYMBOLS_SMOOTH = ["wct_guided_filter", "wct_stylize_smooth"]
 SMOOTH_MAX_RADIUS = 2048                                            # WCT_SMOOTH_MAX_RADIUS
 SMOOTH_EPS = 1e-3                                                   # WCT_SMOOTH_EPS
 
+# every symbol include/wct_hip_transform.h declares (the choice of feature transform); bound from the same libwct_hip.so
+SYMBOLS_TRANSFORM = ["wct_set_transform", "wct_get_transform", "wct_transform_solve"]
+TRANSFORM_WCT, TRANSFORM_OT, TRANSFORM_ADAIN = 0, 1, 2              # WCT_TRANSFORM_*
+TRANSFORMS = {"wct": TRANSFORM_WCT, "ot": TRANSFORM_OT, "adain": TRANSFORM_ADAIN}
+ADAIN_EPS = 1e-5                                                    # WCT_ADAIN_EPS
+
 
 class WctLayer(ctypes.Structure):
     _fields_ = [("cin", c_int), ("cout", c_int), ("pool_after", c_int), ("up_after", c_int),
@@ -171,6 +177,9 @@ def load() -> ctypes.CDLL:
     lib.wct_stylize_color.argtypes = [c_void_p, vp, c_int, c_int, vp, c_int, c_int, c_float, c_int, c_int, vp, ip, ip]
     lib.wct_guided_filter.argtypes = [c_void_p, vp, c_int, c_int, vp, c_int, c_int, c_int, c_double, vp, vp, c_int]
     lib.wct_stylize_smooth.argtypes = [c_void_p, vp, c_int, c_int, vp, c_int, c_int, c_float, c_int, c_int, c_int, c_double, vp, ip, ip]
+    lib.wct_set_transform.argtypes = [c_void_p, c_int]
+    lib.wct_get_transform.argtypes = [c_void_p, ip]
+    lib.wct_transform_solve.argtypes = [c_void_p, c_int, c_int, c_double, vp, vp, vp, c_double, vp, vp, ip]
     lib.wct_workspace_bytes.argtypes = [c_void_p, c_int, c_int, c_int, c_int]
     lib.wct_workspace_bytes.restype = c_size_t
     lib.wct_reserve.argtypes = [c_void_p, c_int, c_int, c_int, c_int]

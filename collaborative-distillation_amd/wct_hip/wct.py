@@ -99,6 +99,8 @@ class WCT:
         self.numpy_variant = bool(getattr(args, "numpy", False))
         if self.numpy_variant:
             self._chk(self._lib.wct_set_numpy_variant(self._ctx, 1))
+        # --transform (include/wct_hip_transform.h): which closed-form feature transform every level applies
+        self.set_transform(getattr(args, "transform", None) or "wct")
         for k in range(1, 6):
             setattr(self, "e%d" % k, _Module(self, "enc", k))
             setattr(self, "d%d" % k, _Module(self, "dec", k))
@@ -335,6 +337,39 @@ class WCT:
         self._chk(self._lib.wct_solve(self._ctx, C, float(n_c), sum_c.data_ptr(), sumsq_c.data_ptr(), float(n_s),
                                       sum_s.data_ptr(), sumsq_s.data_ptr(), alpha, M.data_ptr(), b.data_ptr(),
                                       info if want_info else None))
+        return (M, b, (info[0], info[1])) if want_info else (M, b)
+
+    # ------------------------------------------------------------------ the choice of feature transform (include/wct_hip_transform.h)
+    def set_transform(self, name: str):
+        """"wct" (the reference's whitening / colouring, the default), "ot" (the optimal-transport map between the two Gaussians) or
+        "adain" (per-channel mean / std matching): consumed wherever a level's (M, b) is made.  ValueError for another name, and for
+        a non-wct transform while the numpy variant is on."""
+        if name not in _lib.TRANSFORMS:
+            raise ValueError("transform must be one of %s, not %r" % (sorted(_lib.TRANSFORMS), name))
+        self._chk(self._lib.wct_set_transform(self._ctx, _lib.TRANSFORMS[name]))
+
+    @property
+    def transform_mode(self) -> str:
+        mode = c_int()
+        self._chk(self._lib.wct_get_transform(self._ctx, byref(mode)))
+        return {v: k for k, v in _lib.TRANSFORMS.items()}[mode.value]
+
+    @torch.no_grad()
+    def transform_solve(self, mode: str, n_c, sum_c, sumsq_c, style_stats, alpha: Optional[float] = None, want_info=False):
+        """(M, b) of the transform `mode` from raw content moments and style statistics in the style_export layout
+        (cov_s^(1/2) [C*C] then mu_s [C]); the context's own mode is neither read nor changed."""
+        if mode not in _lib.TRANSFORMS:
+            raise ValueError("transform must be one of %s, not %r" % (sorted(_lib.TRANSFORMS), mode))
+        alpha = self.alpha if alpha is None else float(alpha)
+        C = int(sum_c.numel())
+        sum_c, sumsq_c = self._dev_f64(sum_c, C, "sum_c"), self._dev_f64(sumsq_c, C * C, "sumsq_c")
+        stats = self._dev_f64(style_stats, C * C + C, "style_stats")
+        M = torch.empty(C, C, device=sum_c.device, dtype=torch.float64)
+        b = torch.empty(C, device=sum_c.device, dtype=torch.float64)
+        info = (c_int * 2)()
+        self._stream()
+        self._chk(self._lib.wct_transform_solve(self._ctx, _lib.TRANSFORMS[mode], C, float(n_c), sum_c.data_ptr(), sumsq_c.data_ptr(),
+                                                stats.data_ptr(), alpha, M.data_ptr(), b.data_ptr(), info if want_info else None))
         return (M, b, (info[0], info[1])) if want_info else (M, b)
 
     @torch.no_grad()
@@ -999,7 +1034,8 @@ class WCT:
     def stylize_interp(self, contentImg: torch.Tensor, styles, weights, alpha: Optional[float] = None, num_run: int = 1,
                        out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Style interpolation (-styleInterpWeights): csF = alpha sum_k l_k WCT(cF, style_k) + (1 - alpha) cF at every level, with
-        l = weights / sum(weights) (one finite weight >= 0 per style, sum > 0)."""
+        l = weights / sum(weights) (one finite weight >= 0 per style, sum > 0).  Under set_transform("ot" | "adain") the target is the
+        style whose square-root covariance is the blended slot sum_k l_k S_k (mean sum_k l_k mu_k), no longer the linear mix of the K results."""
         alpha = self.alpha if alpha is None else float(alpha)
         c = self._img(contentImg)
         H, W = int(c.shape[1]), int(c.shape[2])

@@ -492,7 +492,7 @@ int wct_set_conv_mode(wct_ctx* ctx, int mode);
 
 /* `--numpy` of the reference (WCT.py:34, util_wct.py:204-208): whiten_and_color_np adds the identity to the CONTENT
  * covariance before its SVD (util_wct.py:143) -- a different operator from the default path (max-abs 0.49 on a toy case),
- * otherwise the same steps.  0 (default): off. */
+ * otherwise the same steps.  0 (default): off.  A variant of the wct transform only: see wct_hip_transform.h (the choice of transform). */
 int wct_set_numpy_variant(wct_ctx* ctx, int on);
 
 /* 1 (default): the style side of a level (encode, moments, eigen-decomposition -- independent of the content) runs on
