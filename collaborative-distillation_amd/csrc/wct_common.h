@@ -155,6 +155,15 @@ size_t smooth_sums_bytes(long npix);
 size_t smooth_ab_bytes(long npix);
 hipError_t launch_guided_filter(const float* src, int Ho, int Wo, const float* guide, int Hg, int Wg, int r, double eps, float* out_planar,
                                 uint8_t* out_hwc, int round_mode, double* sums, size_t sums_bytes, float* ab, size_t ab_bytes, hipStream_t s);
+// ---- patch swap (swap.hip; include/wct_hip_swap.h).  launch_patch_match: the key norms, then one launch per chunk of `key_chunk` keys, then the
+// read-out; `run` (swap_run_bytes(Nq): the running (score, index) of every query) and `rnorm` (swap_norm_bytes(Nk)) are the caller's scratch; `sat`:
+// the context's saturation counter.  The number of launches is a function of (hs, ws, key_chunk) alone.
+size_t swap_run_bytes(long nq);
+size_t swap_norm_bytes(long nk);
+hipError_t launch_patch_match(const float* q, int h, int w, const float* k, int hs, int ws, int C, int key_chunk, int32_t* idx, float* best,
+                              void* run, size_t run_bytes, float* rnorm, size_t norm_bytes, unsigned* sat, hipStream_t s);
+hipError_t launch_patch_assemble(const int32_t* idx, int h, int w, const float* v, int hs, int ws, int C, const float* base, float alpha, float* out,
+                                 hipStream_t s);
 // *dst = (double)*counter on the stream (wct_range_flag_f64: the saturation counter as a value a sharded run can all-reduce)
 hipError_t launch_counter_to_f64(const unsigned* counter, double* dst, hipStream_t s);
 // ---- image edge: transforms.Resize = Pillow's bilinear resampler, bit-exact (resize.hip)

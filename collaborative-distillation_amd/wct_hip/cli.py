@@ -32,6 +32,11 @@ and --interp_styles / --weightPath).  The files carry _color=<mode> in their nam
 edge structure on the result: wct_guided_filter with the content tensor the cascade was given as colour guide, windows of radius R,
 regulariser --smooth_eps; it runs behind the cascade in every content-driven mode (before the luminance merge of --preserve_color luma),
 with the uint8 conversion fused into whichever kernel comes last.  The files carry _smooth=<R> in their names, after _color=<mode>.
+--swap_level L (not in the reference; Chen & Schmidt 2016, Avatar-Net's style decorator) runs level L (2..5) of the cascade as a patch swap:
+every 3x3 patch of the content feature is replaced by its best-matching style feature patch, matched in the whitened domains of both
+features (--swap_match whitened, the default) or on the features themselves (raw); the other levels keep --transform.  One pair at a time
+(wct_stylize_swap, the serial loop: the swapped level needs the style's feature map, not its statistics); --preserve_color luma and
+--smooth_radius follow as usual.  The files carry _swap=<L> in their names, after the transform mark.
 Decoding/encoding files needs Pillow on the host (the reference's own dependency); the GPU library is mandatory: there
 is no CPU fallback.
 """
@@ -106,6 +111,13 @@ def build_parser() -> argparse.ArgumentParser:
                    help="feature transform of every level: wct = the reference's whitening and colouring, ot = the optimal-transport map "
                         "between the two feature Gaussians (same target statistics, moves the content least), adain = per-channel "
                         "mean / std matching")
+    # not in the reference: patch-based style swap at one cascade level (include/wct_hip_swap.h)
+    p.add_argument("--swap_level", type=int, default=None, choices=[2, 3, 4, 5],
+                   help="run this level of the cascade as a patch swap (style decorator): every 3x3 content feature patch is replaced by "
+                        "its best-matching style patch; the other levels keep --transform (default: off)")
+    p.add_argument("--swap_match", type=str, default=None, choices=["whitened", "raw"],
+                   help="where --swap_level matches patches: whitened = in the whitened domains of both features (Avatar-Net's style "
+                        "decorator, the default), raw = on the features themselves (Chen & Schmidt)")
     return p
 
 
@@ -146,6 +158,9 @@ def out_name(args, imname: str) -> str:
     radius = getattr(args, "smooth_radius", 0)
     transform = getattr(args, "transform", None) or "wct"
     tmark = "_transform=%s" % transform if transform != "wct" else ""                          # directly after alpha; wct names are unchanged
+    swap = getattr(args, "swap_level", None)
+    if swap:
+        tmark += "_swap=%d" % swap                                                              # after the transform mark
     marks = ("_color=%s" % color if color else "") + ("_smooth=%d" % radius if radius else "")   # runs with and without the flags never collide
     return os.path.join(args.outf, "%s_mode=%s_alpha=%s%s%s_%s" % (args.log_mark, args.mode, args.alpha, tmark, marks, imname))
 
@@ -300,6 +315,75 @@ def check_transform_args(args) -> None:
     for flag, name in ((args.numpy, "--numpy"), (args.maskPath is not None, "--maskPath"), (args.weightPath is not None, "--weightPath")):
         if flag:
             raise ValueError("--transform %s does not mix with %s (defined for the wct transform only)" % (transform, name))
+
+
+def check_swap_args(args) -> None:
+    """--swap_level L / --swap_match: one style per content, a content to take patches for, and the plain cascade around the swapped
+    level; --preserve_color luma and --smooth_radius are post-steps and go with it.  Fills in the default match."""
+    from .lib import SWAP_LEVELS, SWAP_MATCHES
+    level, match = getattr(args, "swap_level", None), getattr(args, "swap_match", None)
+    if not level:
+        if match is not None:
+            raise ValueError("--swap_match does nothing without --swap_level")
+        return
+    if level not in SWAP_LEVELS:
+        raise ValueError("--swap_level: one of %s expected, got %r" % (", ".join(str(v) for v in SWAP_LEVELS), level))
+    if match is None:
+        args.swap_match = "whitened"
+    elif match not in SWAP_MATCHES:
+        raise ValueError("--swap_match: whitened or raw expected, got %r" % (match,))
+    clash = [name for flag, name in ((args.synthesis, "--synthesis"), (args.maskPath is not None, "--maskPath"),
+                                     (args.interp_styles is not None, "--interp_styles"), (args.weightPath is not None, "--weightPath"),
+                                     (args.numpy, "--numpy"), (getattr(args, "preserve_color", None) == "match", "--preserve_color match")) if flag]
+    if clash:
+        raise ValueError("--swap_level does not mix with %s" % ", ".join(clash))
+
+
+def _swap_pair(wct, args, logprinter, c_f32, style_f32):
+    """One pair of --swap_level: wct_stylize_swap, and after a clamp of the f16x3 range the same call under the exact-fp32 convolutions
+    (`style_f32()` makes the style tensor afresh for it).  The patch match stays f16x3 in that recompute -- whitened features are O(1) --
+    so a clamp inside it is not cured: it still counts, is reported in the log, and the pair's result is returned all the same."""
+    res = wct.stylize_swap(c_f32, style_f32(), args.swap_level, args.swap_match, args.alpha, args.num_run)
+    if wct.saturation_count(reset=True):
+        logprinter("WARNING: f16x3 range exceeded for this pair -> recomputing it with exact-fp32 convolutions")
+        wct.set_conv_mode("fp32")
+        try:
+            res = wct.stylize_swap(c_f32, style_f32(), args.swap_level, args.swap_match, args.alpha, args.num_run)
+        finally:
+            wct.set_conv_mode("f16x3")
+        # no wct.sync() here: it raises on a clamp; saturation_count synchronises, counts and acknowledges it instead
+        if wct.saturation_count(reset=True):
+            logprinter("WARNING: a feature of this pair left the f16 range inside the patch match and was clamped there; the chosen "
+                       "patches may deviate")
+    return res
+
+
+def run_swap(args, wct, pairs, content_dir, style_dir, logprinter) -> float:
+    """--swap_level: the reference's loop with the cascade of wct_stylize_swap, one pair at a time (the swapped level needs the style's
+    feature map itself, so there are no style statistics to cache); returns the summed per-pair time."""
+    import torch
+    from PIL import Image
+    avg = 0.0
+    style_dev = {}
+    for i, (cfile, sfile) in enumerate(pairs):
+        imname = pair_name(cfile, sfile)
+        logprinter("\n" + "*" * 30 + ' #%s: Transferring "%s" (patch swap at level %d, %s)' % (i, imname, args.swap_level, args.swap_match))
+        c_u8 = torch.from_numpy(load_rgb_u8(os.path.join(content_dir, cfile))).pin_memory().cuda(non_blocking=True)
+        s_u8 = style_dev.get(sfile)
+        if s_u8 is None:
+            s_u8 = torch.from_numpy(load_rgb_u8(os.path.join(style_dir, sfile))).pin_memory().cuda(non_blocking=True)
+            style_dev[sfile] = s_u8
+            while len(style_dev) > 8:
+                style_dev.pop(next(iter(style_dev)))
+        t0 = time.time()
+        c_f32 = _to_tensor(wct, c_u8, args.content_size)
+        res = _swap_pair(wct, args, logprinter, c_f32, lambda: _to_tensor(wct, s_u8, args.style_size))
+        out = _finish_u8(wct, args, res, c_f32).cpu().numpy()   # .cpu() syncs
+        Image.fromarray(out).save(out_name(args, imname))
+        dt = time.time() - t0
+        avg += dt
+        logprinter("Elapsed time is: %.4f seconds" % dt)
+    return avg
 
 
 def _finish_u8(wct, args, res, c_f32):
@@ -775,6 +859,7 @@ def main(argv: Optional[List[str]] = None) -> int:
     check_color_args(args)
     check_smooth_args(args)
     check_transform_args(args)
+    check_swap_args(args)
     os.makedirs(args.outf, exist_ok=True)
     logprinter = LogPrinter(args.debug, os.path.join(args.outf, "log_%s_%s.txt" % (args.log_mark, args.mode)))
     logprinter(sorted(vars(args).items()))
@@ -814,6 +899,13 @@ def main(argv: Optional[List[str]] = None) -> int:
     from .wct import WCT      # raises ImportError if libwct_hip.so is missing: no CPU fallback
     wct = WCT(args)
     logprinter("Number of content-style pairs: %s" % len(pairs))
+    if args.swap_level:
+        if args.pipeline > 0:
+            logprinter("--pipeline is ignored with --swap_level: patch-swap runs use the serial loop")
+        avg = run_swap(args, wct, pairs, content_dir, style_dir, logprinter)
+        if pairs:
+            logprinter("Processed %d images. Average processing time per pair is: %.4f seconds" % (len(pairs), avg / len(pairs)))
+        return 0
     if args.pipeline > 0:
         wall = run_pipelined(args, wct, pairs, content_dir, style_dir, logprinter)
         if pairs:

@@ -49,6 +49,14 @@ TRANSFORM_WCT, TRANSFORM_OT, TRANSFORM_ADAIN = 0, 1, 2              # WCT_TRANSF
 TRANSFORMS = {"wct": TRANSFORM_WCT, "ot": TRANSFORM_OT, "adain": TRANSFORM_ADAIN}
 ADAIN_EPS = 1e-5                                                    # WCT_ADAIN_EPS
 
+# every symbol include/wct_hip_swap.h declares (patch-based style swap at one cascade level); bound from the same libwct_hip.so
+SYMBOLS_SWAP = ["wct_patch_match", "wct_patch_assemble", "wct_swap_level", "wct_stylize_swap"]
+SWAP_WHITENED, SWAP_RAW = 0, 1                                      # WCT_SWAP_*: the match mode
+SWAP_MATCHES = {"whitened": SWAP_WHITENED, "raw": SWAP_RAW}
+SWAP_EPS = 1e-12                                                    # WCT_SWAP_EPS
+SWAP_KEY_CHUNK = 8192                                               # WCT_SWAP_KEY_CHUNK
+SWAP_LEVELS = (2, 3, 4, 5)
+
 
 class WctLayer(ctypes.Structure):
     _fields_ = [("cin", c_int), ("cout", c_int), ("pool_after", c_int), ("up_after", c_int),
@@ -177,6 +185,10 @@ def load() -> ctypes.CDLL:
     lib.wct_stylize_color.argtypes = [c_void_p, vp, c_int, c_int, vp, c_int, c_int, c_float, c_int, c_int, vp, ip, ip]
     lib.wct_guided_filter.argtypes = [c_void_p, vp, c_int, c_int, vp, c_int, c_int, c_int, c_double, vp, vp, c_int]
     lib.wct_stylize_smooth.argtypes = [c_void_p, vp, c_int, c_int, vp, c_int, c_int, c_float, c_int, c_int, c_int, c_double, vp, ip, ip]
+    lib.wct_patch_match.argtypes = [c_void_p, vp, c_int, c_int, vp, c_int, c_int, c_int, vp, vp]
+    lib.wct_patch_assemble.argtypes = [c_void_p, vp, c_int, c_int, vp, c_int, c_int, c_int, vp, c_float, vp]
+    lib.wct_swap_level.argtypes = [c_void_p, c_int, vp, c_int, c_int, vp, c_int, c_int, c_int, c_float, vp, ip, ip]
+    lib.wct_stylize_swap.argtypes = [c_void_p, vp, c_int, c_int, vp, c_int, c_int, c_int, c_int, c_float, c_int, vp, ip, ip]
     lib.wct_set_transform.argtypes = [c_void_p, c_int]
     lib.wct_get_transform.argtypes = [c_void_p, ip]
     lib.wct_transform_solve.argtypes = [c_void_p, c_int, c_int, c_double, vp, vp, vp, c_double, vp, vp, ip]

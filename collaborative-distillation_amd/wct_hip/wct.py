@@ -902,6 +902,93 @@ class WCT:
         self._style_keep = s      # the side stream (and the matching) read it asynchronously
         return out.view(-1)[: 3 * ho.value * wo.value].view(1, 3, ho.value, wo.value)
 
+    # ------------------------------------------------------------------ patch swap (include/wct_hip_swap.h)
+    @staticmethod
+    def _swap_match(what: str, match: str) -> int:
+        if match not in _lib.SWAP_MATCHES:
+            raise ValueError("%s: match must be one of %s, got %r" % (what, ", ".join(repr(m) for m in _lib.SWAP_MATCHES), match))
+        return _lib.SWAP_MATCHES[match]
+
+    @torch.no_grad()
+    def patch_match(self, q: torch.Tensor, k: torch.Tensor, want_best: bool = False):
+        """For every 3x3 patch of the NHWC query map `q` [1,h,w,C] the index of the best-matching 3x3 patch of the key map `k`
+        [1,hs,ws,C] under the key-normalised cross-correlation (wct_patch_match): an int32 tensor [(h-2)*(w-2)], and the winning
+        scores (fp32) with want_best.  The lowest index wins among equal scores."""
+        qf, kf = self._nhwc(q), self._nhwc(k)
+        h, w, C = (int(v) for v in qf.shape)
+        hs, ws, Ck = (int(v) for v in kf.shape)
+        if Ck != C:
+            raise ValueError("patch_match: the maps have %d and %d channels" % (C, Ck))
+        if min(h, w, hs, ws) < 3:
+            raise ValueError("patch_match: maps %dx%d and %dx%d must be at least 3x3" % (h, w, hs, ws))
+        idx = torch.empty((h - 2) * (w - 2), device=qf.device, dtype=torch.int32)
+        best = torch.empty((h - 2) * (w - 2), device=qf.device, dtype=torch.float32) if want_best else None
+        self._stream()
+        self._chk(self._lib.wct_patch_match(self._ctx, qf.data_ptr(), h, w, kf.data_ptr(), hs, ws, C, idx.data_ptr(),
+                                            best.data_ptr() if want_best else None))
+        return (idx, best) if want_best else idx
+
+    @torch.no_grad()
+    def patch_assemble(self, idx: torch.Tensor, h: int, w: int, v: torch.Tensor, base: Optional[torch.Tensor] = None,
+                       alpha: float = 1.0) -> torch.Tensor:
+        """alpha * (the average of the value patches of `v` [1,hs,ws,C] that the queries covering each pixel chose) + (1 - alpha) *
+        `base` [1,h,w,C] (wct_patch_assemble); `base` may be None only with alpha == 1.  Returns [1,h,w,C] fp32."""
+        vf = self._nhwc(v)
+        hs, ws, C = (int(t) for t in vf.shape)
+        h, w = int(h), int(w)
+        if idx.dtype != torch.int32 or idx.numel() != max(h - 2, 0) * max(w - 2, 0):
+            raise ValueError("patch_assemble: idx must be int32 with (h-2)*(w-2) = %d entries" % (max(h - 2, 0) * max(w - 2, 0)))
+        ix = idx.to(self.stats_device).contiguous()
+        bf = None
+        if base is not None:
+            bf = self._nhwc(base)
+            if tuple(bf.shape) != (h, w, C):
+                raise ValueError("patch_assemble: base must be [1,%d,%d,%d], got %s" % (h, w, C, tuple(base.shape)))
+        elif float(alpha) != 1.0:
+            raise ValueError("patch_assemble: base may be None only with alpha == 1")
+        out = torch.empty((1, h, w, C), device=vf.device, dtype=torch.float32)
+        self._stream()
+        self._chk(self._lib.wct_patch_assemble(self._ctx, ix.data_ptr(), h, w, vf.data_ptr(), hs, ws, C,
+                                               bf.data_ptr() if bf is not None else None, float(alpha), out.data_ptr()))
+        return out
+
+    @torch.no_grad()
+    def swap_level(self, level: int, contentImg: torch.Tensor, styleImg: torch.Tensor, match: str = "whitened",
+                   alpha: Optional[float] = None) -> torch.Tensor:
+        """One level with the style decorator instead of an affine transform (wct_swap_level): encode both images, replace every 3x3
+        content patch by its best-matching style patch (`match`: "whitened" = in both whitened domains, "raw" = on the features),
+        blend with the content feature by alpha, decode."""
+        mode = self._swap_match("swap_level", match)
+        alpha = self.alpha if alpha is None else float(alpha)
+        c, s = self._img(contentImg), self._img(styleImg)
+        H, W, Hs, Ws = int(c.shape[1]), int(c.shape[2]), int(s.shape[1]), int(s.shape[2])
+        lv = int(level) if int(level) in (1, 2, 3, 4, 5) else 1
+        out = torch.empty((1, 3, (H >> (lv - 1)) << (lv - 1), (W >> (lv - 1)) << (lv - 1)), device=c.device, dtype=torch.float32)
+        ho, wo = c_int(), c_int()
+        self._stream()
+        self._chk(self._lib.wct_swap_level(self._ctx, int(level), c.data_ptr(), H, W, s.data_ptr(), Hs, Ws, mode, alpha,
+                                           out.data_ptr(), byref(ho), byref(wo)))
+        assert (ho.value, wo.value) == tuple(out.shape[2:])
+        return out
+
+    @torch.no_grad()
+    def stylize_swap(self, contentImg: torch.Tensor, styleImg: torch.Tensor, swap_level: int, match: str = "whitened",
+                     alpha: Optional[float] = None, num_run: int = 1, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The 5 -> 1 cascade with level `swap_level` (2..5) run through swap_level() and every other level through
+        style_transfer_level() under the context's transform, one library call (wct_stylize_swap); bit-identical to that
+        composition."""
+        mode = self._swap_match("stylize_swap", match)
+        alpha = self.alpha if alpha is None else float(alpha)
+        c, s = self._img(contentImg), self._img(styleImg)
+        H, W, Hs, Ws = int(c.shape[1]), int(c.shape[2]), int(s.shape[1]), int(s.shape[2])
+        out = self._out_image(out, H, W)
+        ho, wo = c_int(), c_int()
+        self._stream()
+        self._chk(self._lib.wct_stylize_swap(self._ctx, c.data_ptr(), H, W, s.data_ptr(), Hs, Ws, int(swap_level), mode, alpha,
+                                             int(num_run), out.data_ptr(), byref(ho), byref(wo)))
+        self._style_keep = s      # the side stream reads it asynchronously
+        return out.view(-1)[: 3 * ho.value * wo.value].view(1, 3, ho.value, wo.value)
+
     # ------------------------------------------------------------------ spatial control (regions)
     def _labels(self, labels: torch.Tensor, h: int, w: int) -> torch.Tensor:
         if labels.dtype != torch.uint8 or tuple(labels.shape) != (h, w):
