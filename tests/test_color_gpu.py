@@ -198,9 +198,18 @@ def test_luma_merge_against_the_oracle(torch, wct, Hc, Wc, Ho, Wo):
 
 
 # ---------------------------------------------------------------------------------------------------------------- 5. the cascade
-@pytest.mark.parametrize("H,W,Hs,Ws", [(250, 333, 200, 160), (512, 768, 300, 420)])
-def test_stylize_color_is_the_composition_of_the_public_calls(torch, wct, H, W, Hs, Ws):
+@pytest.mark.parametrize("H,W,Hs,Ws,transform", [
+    pytest.param(250, 333, 200, 160, "wct", id="250-333-200-160"), pytest.param(512, 768, 300, 420, "wct", id="512-768-300-420"),
+    pytest.param(250, 333, 200, 160, "ot", id="250-333-200-160-ot"), pytest.param(250, 333, 200, 160, "adain", id="250-333-200-160-adain")])
+def test_stylize_color_is_the_composition_of_the_public_calls(torch, wct, H, W, Hs, Ws, transform):
+    """Under ot and adain (include/wct_hip_transform.h: the composed entries follow the context's mode) the same identities, on an
+    engine of that mode; the style lane is then waited for BEFORE the content solve."""
     c, s = cu(torch, natural(H, H, W))[None], cu(torch, natural(W, Hs, Ws, cast=(0.5, 1.0, 0.9), shift=(0.3, 0.0, 0.1)))[None]
+    if transform != "wct":
+        under_wct = wct.stylize(c, s, alpha=0.6).clone()
+        wct = sc.make_engine("16x")
+        wct.set_transform(transform)
+        assert not torch.equal(wct.stylize(c, s, alpha=0.6), under_wct)          # the mode took effect
     for alpha, runs in ((1.0, 1), (0.6, 1), (0.6, 2)):
         matched = wct.color_match(s, c)
         plain = wct.stylize(c, s, alpha=alpha, num_run=runs).clone()

@@ -89,13 +89,27 @@ def test_noise_argument_errors(torch_cuda, wct):
 
 
 # ---------------------------------------------------------------------------------------------------------------- synthesize
-@pytest.mark.parametrize("H,W", [(250, 333), (512, 768)])
-@pytest.mark.parametrize("alpha", [1.0, 0.6])
-def test_synthesize_equals_stylize_of_the_oracle_noise(torch_cuda, wct, H, W, alpha):
+@pytest.mark.parametrize("alpha,H,W,transform", [
+    pytest.param(1.0, 250, 333, "wct", id="1.0-250-333"), pytest.param(1.0, 512, 768, "wct", id="1.0-512-768"),
+    pytest.param(0.6, 250, 333, "wct", id="0.6-250-333"), pytest.param(0.6, 512, 768, "wct", id="0.6-512-768"),
+    pytest.param(0.6, 250, 333, "ot", id="0.6-250-333-ot"), pytest.param(0.6, 250, 333, "adain", id="0.6-250-333-adain")])
+def test_synthesize_equals_stylize_of_the_oracle_noise(torch_cuda, wct, H, W, alpha, transform):
+    """Under ot and adain (include/wct_hip_transform.h: the composed entries follow the context's mode) the same identity, on an
+    engine of that mode, and against the prepared cascade."""
     torch = torch_cuda
     g = torch.Generator(device="cuda").manual_seed(H)
     texture = torch.rand((1, 3, 200, 160), device="cuda", generator=g)
     seed = 0x1_0000_0007
+    if transform != "wct":
+        from tests import state_cases as sc
+        under_wct = wct.synthesize(texture, H, W, seed=seed, stream_id=3, alpha=alpha).clone()
+        wct = sc.make_engine("16x")
+        wct.set_transform(transform)
+        assert not torch.equal(wct.synthesize(texture, H, W, seed=seed, stream_id=3, alpha=alpha), under_wct)          # the mode took effect
+        wct.style_prepare(texture)
+        prepared = wct.stylize_prepared(wct.noise(H, W, seed=seed, stream_id=3), alpha=alpha).clone()
+        assert torch.equal(wct.synthesize(None, H, W, seed=seed, stream_id=3, alpha=alpha), prepared)
+        assert torch.equal(wct.synthesize(texture, H, W, seed=seed, stream_id=3, alpha=alpha), prepared)
     direct = wct.stylize(cu(torch, S.noise(seed, H, W, 3))[None], texture, alpha=alpha).clone()
     got = wct.synthesize(texture, H, W, seed=seed, stream_id=3, alpha=alpha)
     assert got.shape == direct.shape == (1, 3, H // 16 * 16, W // 16 * 16)

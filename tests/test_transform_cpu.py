@@ -7,6 +7,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests import transform_cases as TC
 from tests import transform_oracle as O
 from tests.conftest import REPO
 from wct_hip import cli, lib
@@ -88,6 +89,50 @@ def test_oracle_raw_moment_round_trip_and_alpha_blend():
         Ma, ba = O.solve(mode, n, s, ss, O.stats(S, mu_s), 0.6)
         assert np.allclose(Ma, 0.6 * M1 + 0.4 * np.eye(12), atol=1e-13) and np.allclose(ba, 0.6 * b1, atol=1e-13)
         assert np.allclose(M1 @ mu_c + b1, mu_s, atol=1e-10)          # the content mean lands on the style mean
+
+
+# ---------------------------------------------------------------------------------------------------------------- the width sweep's cases
+def test_width_table_reaches_the_branches_it_names():
+    """tests/transform_cases.py: every width even and <= 512, the front end its name claims (solve.hip ns_pad), ragged tiles and k-tails
+    in every class, and the dead channels where the table says they are."""
+    assert list(TC.WIDTHS) == sorted(TC.WIDTHS) and all(C % 2 == 0 and 2 <= C <= 512 for C in TC.WIDTHS)
+    for C, fe in TC.WIDTHS.items():
+        Cp = TC.ns_pad(C)
+        assert {"lds32": Cp == 32, "lds64": Cp == 64, "plain96": Cp == 96, "single128": Cp == 128, "deflated": C > 128}[fe], (C, fe, Cp)
+        a, z = TC.dead_tail(C)
+        assert a % 16 == 0 and a < z == C - 1 and z - a < 16 and a // 16 == TC.tiles(C) - 1
+    for fe, cs in TC.FRONT_ENDS.items():
+        assert any(TC.k_tail(C) for C in cs) and any(C % 16 for C in cs), fe
+    assert sorted({TC.ns_pad(C) for C in TC.FRONT_ENDS["deflated"]}) == [192, 256, 320, 448, 512]      # wide<4> and wide<8>
+    assert sorted({TC.tiles(C) for C in TC.WIDTHS}) == [1, 2, 3, 4, 5, 6, 7, 8, 9, 13, 17, 25, 32]
+    assert len(TC.CASES) == 2 * len(TC.WIDTHS) + len(TC.RANK_WIDTHS)
+    assert len({TC.seed_of(n) for n in TC.CASES}) == len(TC.CASES)
+
+
+@pytest.mark.parametrize("name", list(TC.CASES))
+def test_width_case_is_what_the_table_says(name):
+    """The reference alone: cond(B) on the live block within the solver's gates (gate_for of the GPU test cannot trip), the intended
+    rank, and -- where the content has full rank on its live channels -- the textbook form of the ot map against S B^(-1/2) S."""
+    spec = TC.CASES[name]
+    C = spec["C"]
+    n, s, ss, st = TC.build(name)
+    d = TC.describe(n, s, ss, st)
+    print("%s: cond(B) %.2e rank %d live %d rank_c %d" % (name, d["cond"], d["rank"], d["live"], d["rank_c"]))
+    assert d["cond"] <= 1e10
+    dead = spec.get("dead_c", ())
+    if "rank_c" in spec:
+        assert n == C - 11 and d["live"] == C and d["rank_c"] == spec["rank_c"] == d["rank"] == C - 12      # singular by rank, not by dead channels
+        return                                                                        # (the textbook form needs cov_c^(-1/2): not the same operator here)
+    assert d["live"] == C - len(dead) == d["rank"] == d["rank_c"]
+    assert d["cond"] <= 1e6                                                           # the 1e-8 gate
+    live = [i for i in range(C) if i not in dead]
+    _, cov_c = O.mean_cov(n, s, ss)
+    S, _ = O.split_stats(st)
+    ix = np.ix_(live, live)
+    T = O.T_ot(cov_c, S)
+    assert np.count_nonzero(T[list(dead), :]) == 0 and np.count_nonzero(T[:, list(dead)]) == 0
+    err = O.rel_fro(T[ix], O.T_ot_sigma_form(cov_c[ix], (S @ S)[ix]))
+    assert err < 1e-9, (name, err)
 
 
 # ---------------------------------------------------------------------------------------------------------------- header and bindings

@@ -15,6 +15,7 @@ import pytest
 
 from tests import state_cases as sc
 from tests import transform_oracle as O
+from tests.transform_cases import make_case as _case
 from tests.conftest import PKG, REPO, rel_err
 from wct_hip import lib as _lib
 
@@ -85,22 +86,6 @@ def check_solve(torch, eng, mode, n, s, ss, st, alpha, what, want_ns=None):
 
 
 # ------------------------------------------------------------------------------------------------ 1. raw moments
-def _case(seed, C, lo_c, lo_s, n=50000, dead_c=(), dead_s=(), rank_c=None, rank_s=None):
-    rng = np.random.default_rng(seed)
-    cov_c = O.spd(rng, C, lo_c, dead_c, rank_c)
-    cov_s = O.spd(rng, C, lo_s, dead_s, rank_s)
-    mu_c, mu_s = rng.random(C), rng.random(C)
-    for d in dead_c:
-        mu_c[d] = 0.0
-    for d in dead_s:
-        mu_s[d] = 0.0
-    n, s, ss = O.raw(n, mu_c, cov_c)
-    S = O.sym_pow(cov_s, 0.5)
-    S[list(dead_s), :] = 0.0                    # a slot's dead channels are exact zeros (solve.hip zeroes them in its result)
-    S[:, list(dead_s)] = 0.0
-    return n, s, ss, O.stats(S, mu_s)
-
-
 DEAD29 = tuple(range(3, 128, 4))[:29]
 RAW_CASES = {
     "C24": dict(C=24, lo_c=1e-2, lo_s=1e-2),
@@ -256,11 +241,11 @@ def test_wct_mode_is_untouched_by_a_detour_through_the_other_modes(torch):
 
 
 # ------------------------------------------------------------------------------------------------ 6. state under ot
-STATE_CASES = ("stylize/small", "prepared/small", "solve/small")
+STATE_CASES = ("stylize/small", "prepared/small", "solve/small", "level/small", "transform/small", "split_level/small", "interp/small", "synthesize/small")
 
 
-def _ot_engine():
-    e = sc.make_engine("16x")
+def _ot_engine(kind="16x"):
+    e = sc.make_engine(kind)
     e.set_transform("ot")
     return e
 
@@ -272,12 +257,13 @@ def _equal(torch, got, want, what):
         assert torch.equal(got[k], want[k]), "%s: %s differs" % (what, k)
 
 
-def test_state_under_ot(torch):
-    want = {name: sc.run(_ot_engine(), name) for name in STATE_CASES}
+def _state_under_ot(torch, kind):
+    assert all(sc.CASES[name].wide for name in STATE_CASES)
+    want = {name: sc.run(_ot_engine(kind), name) for name in STATE_CASES}
     torch.cuda.synchronize()
-    differs = sc.run(sc.make_engine("16x"), "stylize/small")
+    differs = sc.run(sc.make_engine(kind), "stylize/small")
     assert not torch.equal(differs["alpha1"], want["stylize/small"]["alpha1"])          # the cases do run under ot
-    used = _ot_engine()
+    used = _ot_engine(kind)
     used.stylize(sc.image(7, 72, 88), sc.image(8, 66, 70))
     used.transform_solve("adain", *sc.raw_moments(9, 32, 5000, 1e-2), torch.rand(32 * 33, dtype=torch.float64))
     for name in reversed(STATE_CASES):
@@ -286,12 +272,45 @@ def test_state_under_ot(torch):
         allocs = used.debug_get("ws_allocs")
         _equal(torch, sc.run(used, name), want[name], "second call, " + name)
         assert used.debug_get("ws_allocs") == allocs, name
-    poisoned = _ot_engine()
+    poisoned = _ot_engine(kind)
     poisoned.debug_set("poison", 0xA5)
     for name in STATE_CASES:
         _equal(torch, sc.run(poisoned, name), want[name], "poison 0xA5, " + name)
         poisoned.debug_set("poison", 0xA5)
         _equal(torch, sc.run(poisoned, name), want[name], "poison 0xA5 again, " + name)
+    poisoned.debug_set("poison", -1)
+    assert used.saturation_count() == 0 and poisoned.saturation_count() == 0
+
+
+def test_state_under_ot(torch):
+    _state_under_ot(torch, "16x")
+
+
+@pytest.fixture(scope="module")
+def wide_state(torch):
+    """(an un-pruned ot engine with a past, one whose scratch is poisoned between calls), shared by the cases below."""
+    used, poisoned = _ot_engine("wide"), _ot_engine("wide")
+    used.stylize(sc.image(7, 72, 88), sc.image(8, 66, 70))
+    used.transform_solve("adain", *sc.raw_moments(9, 32, 5000, 1e-2), torch.rand(32 * 33, dtype=torch.float64))
+    return used, poisoned
+
+
+@pytest.mark.parametrize("name", STATE_CASES)
+def test_state_under_ot_wide_model(torch, wide_state, name):
+    """The same legs on the un-pruned engine, one case at a time: the C > 128 solves of a call are deferred to its end (ok_log), and
+    under ot the content side runs ot_sandwich -> B^(-1/2) -> ot_assemble between the deferred outcome slots."""
+    used, poisoned = wide_state
+    want = sc.run(_ot_engine("wide"), name)
+    torch.cuda.synchronize()
+    if name == "stylize/small":
+        assert not torch.equal(sc.run(sc.make_engine("wide"), name)["alpha1"], want["alpha1"])          # the cases do run under ot
+    _equal(torch, sc.run(used, name), want, "used engine, " + name)
+    allocs = used.debug_get("ws_allocs")
+    _equal(torch, sc.run(used, name), want, "second call, " + name)
+    assert used.debug_get("ws_allocs") == allocs, name                      # second call of a size: nothing is allocated
+    for leg in ("poison 0xA5, ", "poison 0xA5 again, "):
+        poisoned.debug_set("poison", 0xA5)
+        _equal(torch, sc.run(poisoned, name), want, leg + name)
     poisoned.debug_set("poison", -1)
     assert used.saturation_count() == 0 and poisoned.saturation_count() == 0
 
