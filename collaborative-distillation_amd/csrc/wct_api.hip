@@ -143,6 +143,8 @@ struct wct_ctx {
   // sat_dev is a 256-byte block of counters (unsigned): [0] the saturation counter; [1] its snapshot at the start of a deferred
   // wide-model call (with_deferred_solves); [2], [3] single-launch Newton-Schulz solves that ABORTED on the main / side lane
   unsigned* sat_host = nullptr;  // pinned host mirror, refreshed asynchronously at the end of every compute entry point (wct_range_poll)
+  // sat_host[SAT_SIDE_WORD]: the side lane's own mirror of counter [0] (range_readback_side).  Two words, one per stream: each is written in
+  // its stream's order, so neither can be overwritten by an older value of the other stream's copy; wct_range_poll reports the larger
   // RCCL communicator of a column-sharded job (wct_comm_*, wct_level_sharded); the library resolves RCCL at run time (no link-time dependency)
   void* comm = nullptr;
   bool comm_owned = false;
@@ -253,6 +255,21 @@ struct DevGuard {
   DevGuard& operator=(const DevGuard&) = delete;
 };
 #define WCT_GUARD(ctx) DevGuard dev_guard__(ctx)
+
+constexpr int SAT_SIDE_WORD = 4;
+
+void range_host_set(wct_ctx* ctx, unsigned n) {    // both lanes idle (the callers have synchronised them)
+  if (ctx->sat_host) ctx->sat_host[0] = ctx->sat_host[SAT_SIDE_WORD] = n;
+}
+
+// An entry point whose clamping kernels ran on the SIDE lane and that does not join the caller's stream to it (wct_style_prepare*: the
+// style side is meant to overlap whatever the caller enqueues next) mirrors the counter on that lane, behind those kernels in stream
+// order -- the caller's stream neither waits for the side lane nor does the host
+int range_readback_side(wct_ctx* ctx, Lane& ln) {
+  if (ctx->quiet_readback || &ln == &ctx->main) return WCT_OK;
+  if (ctx->sat_host) HIPCHK(ctx, hipMemcpyAsync(ctx->sat_host + SAT_SIDE_WORD, ctx->sat_dev, sizeof(unsigned), hipMemcpyDeviceToHost, ln.stream));
+  return WCT_OK;
+}
 
 // the saturation counter follows every compute entry point to pinned host memory on the caller's stream (4 bytes, no sync):
 // wct_range_poll then reports a clamp of any COMPLETED call without stalling the pipeline
@@ -850,7 +867,7 @@ int with_deferred_solves(wct_ctx* ctx, bool wait_side, BODY&& body) {
   unsigned before = 0;
   HIPCHK(ctx, hipMemcpy(&before, ctx->sat_dev + 1, sizeof(unsigned), hipMemcpyDeviceToHost));
   HIPCHK(ctx, hipMemcpy(ctx->sat_dev, &before, sizeof(unsigned), hipMemcpyHostToDevice));
-  if (ctx->sat_host) *ctx->sat_host = before;
+  range_host_set(ctx, before);
   return body();     // defer_big is off: every solve checks (and repairs) itself
 }
 
@@ -1220,7 +1237,7 @@ int wct_sync(wct_ctx* ctx) {
     // reported ONCE and cleared: a later WCT_ERR_RANGE then means a later clamp, not a stale flag (the total stays readable
     // through wct_saturation_count until this point only)
     HIPCHK(ctx, hipMemset(ctx->sat_dev, 0, sizeof n));
-    if (ctx->sat_host) *ctx->sat_host = 0u;
+    range_host_set(ctx, 0u);
     return fail(ctx, WCT_ERR_RANGE, "%u thread(s) clamped an activation to the f16x3 range (|x| > 65504, or NaN) since the last report: results "
                 "deviate from the fp32 reference; use conv mode 0 (exact fp32) for these weights / inputs.  The flag is now cleared", n);
   }
@@ -1235,14 +1252,15 @@ int wct_saturation_count(wct_ctx* ctx, int reset, unsigned long long* count) {
   unsigned n = 0;
   HIPCHK(ctx, hipMemcpy(&n, ctx->sat_dev, sizeof n, hipMemcpyDeviceToHost));
   if (reset && n) HIPCHK(ctx, hipMemset(ctx->sat_dev, 0, sizeof n));
-  if (ctx->sat_host) *ctx->sat_host = reset ? 0u : n;
+  range_host_set(ctx, reset ? 0u : n);
   if (count) *count = n;
   return WCT_OK;
 }
 
 int wct_range_poll(wct_ctx* ctx, unsigned long long* count) {
   if (!ctx || !count) return WCT_ERR_INVALID;
-  *count = ctx->sat_host ? *reinterpret_cast<volatile unsigned*>(ctx->sat_host) : 0u;
+  const volatile unsigned* m = reinterpret_cast<volatile unsigned*>(ctx->sat_host);
+  *count = m ? std::max(m[0], m[SAT_SIDE_WORD]) : 0u;     // the caller's stream's mirror and the side lane's (range_readback_side)
   return WCT_OK;
 }
 
@@ -1623,13 +1641,17 @@ int wct_style_prepare_levels(wct_ctx* ctx, const float* style, int Hs, int Ws, u
   if (!ctx) return WCT_ERR_INVALID;
   WCT_GUARD(ctx);
   if (!style) return fail(ctx, WCT_ERR_INVALID, "style_prepare: NULL style");
-  return with_deferred_solves(ctx, true, [&]() -> int {
-    if (int rc = fork_side(ctx)) return rc;
-    for (int level = 5; level >= 1; --level)
-      if ((level_mask >> level & 1u) && ctx->mod[WCT_KIND_ENC][level].loaded)
-        if (int rc = style_side(ctx, level, style, Hs, Ws)) return rc;
-    return WCT_OK;
-  });
+  if (int rc = with_deferred_solves(ctx, true, [&]() -> int {
+        if (int rc = fork_side(ctx)) return rc;
+        for (int level = 5; level >= 1; --level)
+          if ((level_mask >> level & 1u) && ctx->mod[WCT_KIND_ENC][level].loaded)
+            if (int rc = style_side(ctx, level, style, Hs, Ws)) return rc;
+        return WCT_OK;
+      })) return rc;
+  // the encoders ran on the side lane (with overlap on): the mirror goes behind them on that lane, so that the caller's stream stays
+  // free to overlap the style side; with overlap off everything ran on the caller's stream
+  if (int rc = range_readback_side(ctx, ctx->overlap ? ctx->side : ctx->main)) return rc;
+  return range_readback(ctx);
 }
 
 int wct_style_prepare(wct_ctx* ctx, const float* style, int Hs, int Ws) { return wct_style_prepare_levels(ctx, style, Hs, Ws, 0x3eu); }
@@ -1703,7 +1725,7 @@ int wct_content_encode(wct_ctx* ctx, int level, const float* content, int H, int
   ctx->pair_open = true;
   if (h_out) *h_out = h;
   if (w_out) *w_out = w;
-  return WCT_OK;
+  return range_readback(ctx);
 }
 
 int wct_content_solve(wct_ctx* ctx, int level, double n_c, const double* sum_c, const double* sumsq_c, float alpha, double* M,

@@ -96,7 +96,13 @@ int wct_sync(wct_ctx* ctx);
  *   wct_sync              reports a non-zero counter as WCT_ERR_RANGE once and clears it
  *   wct_range_poll        NO synchronisation: every compute entry point ends with an asynchronous 4-byte copy of the counter
  *                         to pinned host memory on the caller's stream; this returns the last copy that has landed, i.e. the
- *                         state after some COMPLETED call (callers check it at the start of their next call)
+ *                         state after some COMPLETED call (callers check it at the start of their next call).  A call is
+ *                         complete when ALL the work it enqueued has run.  wct_style_prepare[_levels] runs its encoders on the
+ *                         context's side stream and does not join the caller's stream to it (the style side overlaps what the
+ *                         caller enqueues next): its copy is made on the side stream, behind those encoders, so a clamp of
+ *                         the style side shows here once the side stream has drained (a device synchronisation, wct_sync, or
+ *                         any later call that consumes the style statistics and has itself completed) -- waiting for the
+ *                         caller's stream alone is not enough for this one entry point
  *   wct_range_flag_f64    writes the counter as one double to flag_dev on the caller's stream, so that a sharded run can fold it
  *                         into the all-reduce of the moments it already makes and every rank sees every rank's clamps
  * Conv mode 0 (exact fp32 MFMA) has no such limit. */
