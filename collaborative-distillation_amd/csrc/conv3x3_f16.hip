@@ -331,7 +331,7 @@ __global__ __launch_bounds__(256) void conv3x3_f16_c16_kernel(F16Args a) {
       }
       const int oy = (ty0 + wave * 2) >> 1, ox = gx >> 1;
       if (!(li & 1) && oy < Hp && ox < Wp && co < a.cout) {
-        if (a.out_sp) sp16_store4(reinterpret_cast<char*>(a.out) + ((size_t)oy * Wp + ox) * a.cout * 4, kq, m, sat, a.relu != 0);
+        if (a.out_sp) sp16_store4(reinterpret_cast<char*>(a.out) + ((size_t)oy * Wp + ox) * 64, kq, m, sat, a.relu != 0);   // 64-byte records whatever cout (8: half of it unused)
         else *reinterpret_cast<f32x4*>(a.out + ((size_t)oy * Wp + ox) * a.cout + co) = m;
       }
     } else {
@@ -352,7 +352,7 @@ __global__ __launch_bounds__(256) void conv3x3_f16_c16_kernel(F16Args a) {
               a.out[2 * plane + off] = v[2];
             }
           } else if (co < a.cout) {
-            if (a.out_sp) sp16_store4(reinterpret_cast<char*>(a.out) + ((size_t)gy * a.W + gx) * a.cout * 4, kq, v, sat, a.relu != 0);
+            if (a.out_sp) sp16_store4(reinterpret_cast<char*>(a.out) + ((size_t)gy * a.W + gx) * 64, kq, v, sat, a.relu != 0);
             else *reinterpret_cast<f32x4*>(a.out + ((size_t)gy * a.W + gx) * a.cout + co) = v;
           }
         }

@@ -399,10 +399,12 @@ hipError_t launch_fold_affine(const float* w, const float* bias, int cout, int c
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fold_block_kernel<OB>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
     const int ipad = (cin + 15) / 16 * 16;
+    note_launch_text("fb");
     hipLaunchKernelGGL(fold_block_kernel<OB>, dim3((unsigned)((cout_pad + OB - 1) / OB), (unsigned)((ipad + 255) / 256)), dim3(256), lds, s, w, bias,
                        cout, cin, cout_pad, M, b, wpk_out, bias_out, maxbits_dev);
     return hipGetLastError();
   }
+  { const int ipad = (cin + 15) / 16 * 16; note_launch_text(256 % ipad == 0 ? "fra" : "frg"); }   // fold_row_kernel's aligned / generic path
   hipLaunchKernelGGL(fold_row_kernel, dim3((unsigned)cout_pad), dim3(256), (size_t)cin * 9 * sizeof(float), s, w, bias, cout, cin, cout_pad, M, b,
                      wpk_out, bias_out, maxbits_dev);
   return hipGetLastError();
@@ -431,6 +433,7 @@ hipError_t launch_fold_fast(const float* w, const float* bias, int cout, int cin
   const double* Ws = style_buf;
   const double* WsumS = Ws + (size_t)cout * 9 * cin;
   const double* Wmus = WsumS + (size_t)cout * cin;
+  note_launch_text("ff");
   hipLaunchKernelGGL(fold_fast_kernel, dim3((unsigned)cout_pad), dim3(FOLD_NT), (size_t)(10 * cin + fold_part_doubles(10)) * sizeof(double), s, w, bias,
                      cout, cin, cout_pad, Ws, WsumS, Wmus, Wc, mu_c, alpha, wpk_out, bias_out, rowmax_dev);
   return hipGetLastError();

@@ -848,6 +848,7 @@ hipError_t launch_moments(const float* feat, int C, int h, int wfull, int x0, in
       hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kr), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsr);
       if (e != hipSuccess) return e;
     }
+    note_moments_form('r', 256, 16, a.NP, false, true);   // 256 pixels per pass of the workgroup, 16 loads per lane and block, NP products
     hipLaunchKernelGGL(kr, dim3((unsigned)a.NPC), dim3(256), ldsr, s, a);
     const long ne = (long)a.NP * 256 + a.T * 16;
     hipLaunchKernelGGL(moments_reduce_kernel, dim3((unsigned)((ne + 15) / 16)), dim3(256), 0, s, a, sum, sumsq);
@@ -867,6 +868,7 @@ hipError_t launch_moments(const float* feat, int C, int h, int wfull, int x0, in
     blk_plan(C, npix, a.chunk, a.NPC);
     if (ws_bytes < ((size_t)a.NPC * a.NP * 256 + (size_t)a.NPC * a.T * 16) * sizeof(double)) return hipErrorOutOfMemory;
     a.part_sum = a.part_sq + (size_t)a.NPC * a.NP * 256;
+    note_moments_form('b', 64, 2, f32_products ? 8 : 4, false, f32_products);   // chunks of 64 pixels, two steps of loads in flight, waves
     if (f32_products) hipLaunchKernelGGL((moments_blk_kernel<true, 8>), dim3((unsigned)a.NPC, (unsigned)nbp), dim3(512), 0, s, a);
     else hipLaunchKernelGGL((moments_blk_kernel<false, 4>), dim3((unsigned)a.NPC, (unsigned)nbp), dim3(256), 0, s, a);
     const long ne = (long)a.NP * 256 + a.T * 16;
@@ -876,6 +878,7 @@ hipError_t launch_moments(const float* feat, int C, int h, int wfull, int x0, in
   size_t lds = (size_t)a.MP * a.Cs * sizeof(float);
   if (a.pixsplit) lds = std::max(lds, ((size_t)4 * a.NP * 256 + 4 * a.T * 16) * sizeof(double));
   const int nld = (a.MP * (C / 4) + 255) / 256;
+  note_moments_form('l', a.MP, nld < MAXLD ? nld : MAXLD, a.pw, a.pixsplit != 0, f32_products);
   auto go = [&](auto kern) -> hipError_t {
     if (lds > 48 * 1024) {
       hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);

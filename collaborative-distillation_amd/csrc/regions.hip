@@ -361,6 +361,7 @@ hipError_t launch_moments_labeled(const float* feat, int C, long npix, const uin
     hipLaunchKernelGGL(kern, dim3((unsigned)a.NPC, (unsigned)npg, (unsigned)K), dim3(256), lds, s, a);
     return hipGetLastError();
   };
+  note_moments_form('l', a.MP, (a.MP * (C >> 2) + 255) / 256, a.PW, false, f32_products);
   hipError_t e;
   if (a.PW == 2) e = f32_products ? go(moments_labeled_kernel<2, true>) : go(moments_labeled_kernel<2, false>);
   else e = f32_products ? go(moments_labeled_kernel<8, true>) : go(moments_labeled_kernel<8, false>);

@@ -1195,6 +1195,7 @@ hipError_t launch_fold_gemm(const double* rows, const float* bias, int cout, int
   }
   constexpr int NS = 8;
   const dim3 grid((unsigned)(cin / 32), (unsigned)(cout * 9 / 32 + (cout_pad + NS - 1) / NS));
+  note_launch_text("fg");
   hipLaunchKernelGGL(fold_gemm_kernel<NS>, grid, dim3(64 * NS), 0, s, rows, rows + (size_t)cout * 9 * cin, bias, cout, cin, cout_pad, M, b, wpk_out,
                      bias_out, maxbits_dev);
   return hipGetLastError();

@@ -65,7 +65,7 @@ struct ProfRec {
 
 }  // namespace
 
-__thread LaunchForm wct_launch_form = {0, 0, false};   // wct_common.h
+__thread LaunchForm wct_launch_form = {0, 0, false, {0}};   // wct_common.h
 
 // An in-order execution lane: a stream plus the scratch only that stream touches.  `main` runs on the caller's
 // stream (content side, assembly, decode); `side` is a context-owned stream on which the style side (encode,
@@ -339,7 +339,7 @@ struct ProfScope {
   ProfScope(wct_ctx* c, hipStream_t stream, const char* name, double flops, double bytes) : ctx(c), st(stream), on(c->prof) {
     if (!on) return;
     r.name = name; r.flops = flops; r.bytes = bytes; r.side = stream == c->side.stream;
-    wct_launch_form = LaunchForm{0, 0, false};
+    wct_launch_form = LaunchForm{0, 0, false, {0}};
     (void)hipEventCreate(&r.e0); (void)hipEventCreate(&r.e1);
     (void)hipEventRecord(r.e0, st);
   }
@@ -347,7 +347,10 @@ struct ProfScope {
     if (!on) return;
     (void)hipEventRecord(r.e1, st);
     // debug key "prof_forms": what the size-selected launcher inside this scope chose, e.g. "dec_tail_fused<16-16-3>#u16m"
-    if (ctx->prof_forms && wct_launch_form.form) {
+    if (ctx->prof_forms && wct_launch_form.text[0]) {
+      r.name += ":";                       // ':' not '#': tests tell the conv forms from everything else by the '#'
+      r.name += wct_launch_form.text;      // the plan-driven launchers' own suffix (moments family, folds)
+    } else if (ctx->prof_forms && wct_launch_form.form) {
       char sfx[16];
       snprintf(sfx, sizeof sfx, "#%c%d%s", wct_launch_form.form, wct_launch_form.tile_h, wct_launch_form.multi ? "m" : "");
       r.name += sfx;
@@ -630,7 +633,14 @@ void free_module(Module& m) {
 }
 
 size_t max_act_bytes(const Module& m, int H, int W, bool enc) {
-  // largest intermediate NHWC activation of a module run on an H x W image (enc) / h x w feature (dec)
+  // largest intermediate activation of a module run on an H x W image (enc) / h x w feature (dec).  Per pixel: whole 16-channel chunks --
+  // an SP16 tensor (conv_f16_dev.h) is ceil(cout / 16) planes of 64-byte records, more than the cout * 4 bytes of fp32 NHWC wherever cout
+  // is no multiple of 16 (8, 24, 40, ...): sized by cout * 4, a layer's SP16 output ran past the buffer
+  // (the last layer writes fp32 into the caller's buffer, never SP16)
+  auto px_bytes = [&](size_t i) {
+    const int cout = m.layers[i].d.cout;
+    return (size_t)(i + 1 < m.layers.size() ? (cout + 15) / 16 * 16 : cout) * sizeof(float);
+  };
   size_t best = 0;
   int h = H, w = W;
   for (size_t i = 0; i < m.layers.size(); ++i) {
@@ -638,11 +648,11 @@ size_t max_act_bytes(const Module& m, int H, int W, bool enc) {
     if (enc) {
       int oh = h, ow = w;
       if (l.pool_after) { oh = h / 2; ow = w / 2; }
-      best = std::max(best, (size_t)oh * ow * l.d.cout * sizeof(float));
+      best = std::max(best, (size_t)oh * ow * px_bytes(i));
       h = oh; w = ow;
     } else {
       if (i > 0 && m.layers[i - 1].up_after) { h *= 2; w *= 2; }
-      best = std::max(best, (size_t)h * w * l.d.cout * sizeof(float));
+      best = std::max(best, (size_t)h * w * px_bytes(i));
     }
   }
   return best;

@@ -5,6 +5,7 @@
 #include <stddef.h>
 
 #include <stdlib.h>
+#include <stdio.h>
 #include <vector>
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -23,12 +24,20 @@ static inline const char* wct_debug_env(const char* name) {
 // wct_api.hip's ProfScope appends it to the profile record's name as "#<form><tile_h>[m]" when wct_debug_set("prof_forms", 1) is on
 // (tests/test_geometry_gpu.py).  form: 'r' two-role head, 't' plain nine-tap tiles, 'u' upsample (2x2 per parity) form, 's' small-map
 // form, '3' three-stage persistent kernel; 0 = the launcher has a single form and says nothing.  multi: the grid is smaller than
-// tiles x cout groups, so some workgroup walks more than one unit.  Defined in wct_api.hip; not part of the ABI.
-struct LaunchForm { char form; int tile_h; bool multi; };
+// tiles x cout groups, so some workgroup walks more than one unit.
+// The plan-driven launchers of the feature-space kernels (launch_moments, launch_moments_labeled, launch_moments_weighted, the fold
+// launchers) leave a ready-made suffix in `text` instead (note_launch_text; grammar: include/wct_hip.h, "prof_forms"); ProfScope
+// appends ":<text>" (tests/test_sweep_gpu.py holds it against tests/sweep_cases.py).  Defined in wct_api.hip; not part of the ABI.
+struct LaunchForm { char form; int tile_h; bool multi; char text[24]; };
 extern __thread LaunchForm wct_launch_form __attribute__((visibility("hidden")));
 static inline void note_launch_form(char form, int tile_h, long units, long grid) {
   wct_launch_form.form = form; wct_launch_form.tile_h = tile_h; wct_launch_form.multi = units > grid;
 }
+// moments family: "<family><MP>.<NLD>.<PW>[s]<d|f>" (s: pixel split; d / f: fp64 / fp32-block products)
+static inline void note_moments_form(char family, int mp, int nld, int pw, bool pixsplit, bool f32) {
+  snprintf(wct_launch_form.text, sizeof wct_launch_form.text, "%c%d.%d.%d%s%c", family, mp, nld, pw, pixsplit ? "s" : "", f32 ? 'f' : 'd');
+}
+static inline void note_launch_text(const char* text) { snprintf(wct_launch_form.text, sizeof wct_launch_form.text, "%s", text); }
 
 // The context's saturation counter (wct_api.hip sat_dev): +1 per thread (or wave) that clamped an activation, SATURATING -- the
 // thread that wraps the 32-bit counter sees old == 0xffffffff itself and pins it at 2^31 (so does every add above it).

@@ -123,7 +123,16 @@ int wct_range_flag_f64(wct_ctx* ctx, double* flag_dev);
  * kernel form the size-selected launchers chose, "#<form><tile height>[m]" -- form r = two-role head, t = plain tiles, u = upsample
  * (2x2 per parity) form, s = small-map form, 3 = three-stage persistent kernel; m = the grid is smaller than tiles x cout groups, so a
  * workgroup walks several units -- e.g. "dec_tail_fused<16-16-3>#u16m".  Launchers with one form add nothing; with the switch off the
- * names are unchanged (tests/test_geometry_gpu.py).
+ * names are unchanged (tests/test_geometry_gpu.py).  The launchers of the feature-space kernels, whose tiling is a function of the
+ * channel count and the pixel count, report behind a ':' instead (so that '#' keeps meaning "a conv form"):
+ *   "moments", "moments_labeled", "moments_weighted"   ":<family><MP>.<NLD>.<PW>[s]<d|f>" -- family l = LDS-tile kernel (MP pixels per
+ *                  tile, NLD float4 loads per thread and tile, PW tile pairs per wave, s = the waves split the tile's pixels), r =
+ *                  moments_reg_kernel (C = 32 / 64 with fp32 products: 256 pixels per pass, 16 loads, PW = its tile pairs), b =
+ *                  moments_blk_kernel (chunks of 64 pixels, 2 steps of loads in flight, PW = its waves); d / f = fp64 / fp32-block
+ *                  products -- e.g. "moments:l128.6.6sd", "moments_labeled:l64.2.2f"
+ *   "fold_affine"  ":fra" / ":frg" = fold_row_kernel's aligned / generic path, ":fb" = fold_block_kernel (cin >= 256), ":fg" = the fp64
+ *                  GEMM fold, ":ff" = the fast fold
+ * (tests/sweep_cases.py restates the plans, tests/test_sweep_gpu.py holds every report against it).
  * "poison" (a byte 0..255, or -1 = off) is the test hook for "does a call read what an earlier call left in the workspace": it
  * synchronises both of the context's streams, fills every allocated SCRATCH buffer of the context with that byte and, until it is
  * turned off, every buffer the workspace allocates later as well (a grown buffer is a fresh allocation and usually zero pages).

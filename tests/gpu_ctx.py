@@ -1,5 +1,5 @@
 """One wct_ctx driven through the C ABI with numpy in and numpy out: the harness of the GPU tests that load modules of their own
-(tests/test_widths_gpu.py, tests/test_range_gpu.py).  The WCT class hard-codes model_zoo's widths; `wct_load_module` takes any layer list."""
+(tests/test_widths_gpu.py, tests/test_range_gpu.py, tests/test_sweep_gpu.py).  The WCT class hard-codes model_zoo's widths; `wct_load_module` takes any layer list."""
 import ctypes
 from ctypes import byref, c_int, c_void_p
 
@@ -189,3 +189,98 @@ class Ctx:
         C, h, w = c_int(), c_int(), c_int()
         self.chk(self.L.wct_feature_shape(self.ctx, level, H, W, byref(C), byref(h), byref(w)))
         return C.value, h.value, w.value
+
+    # ---- the un-fused feature-space entries (tests/test_sweep_gpu.py); features are h x w x C (NHWC) unless nchw is set
+    def _layout(self, feat, nchw):
+        """-> (device tensor, C, h, w, layout id); nchw: feat is C x h x w"""
+        if nchw:
+            C, h, w = feat.shape
+        else:
+            h, w, C = feat.shape
+        return self.dev(feat, np.float32), C, h, w, _lib.LAYOUT_NCHW if nchw else _lib.LAYOUT_NHWC
+
+    def apply(self, feat, M, b, nchw=False):
+        f, C, h, w, layout = self._layout(feat, nchw)
+        Md, bd = self.dev(M, np.float64), self.dev(b, np.float64)
+        out = self.t.empty_like(f)
+        self.sync()
+        self.chk(self.L.wct_apply(self.ctx, f.data_ptr(), C, h, w, layout, Md.data_ptr(), bd.data_ptr(), out.data_ptr()))
+        self.sync()
+        return out.cpu().numpy()
+
+    def moments_labeled(self, feat_hwc, lab, K):
+        """-> n [K], sum [K, C], sumsq [K, C, C]"""
+        h, w, C = feat_hwc.shape
+        f, l = self.dev(feat_hwc, np.float32), self.dev(lab, np.uint8)
+        n = self.t.empty(K, device="cuda", dtype=self.t.float64)
+        s = self.t.empty((K, C), device="cuda", dtype=self.t.float64)
+        ss = self.t.empty((K, C, C), device="cuda", dtype=self.t.float64)
+        self.sync()
+        self.chk(self.L.wct_moments_labeled(self.ctx, f.data_ptr(), C, h, w, l.data_ptr(), K, n.data_ptr(), s.data_ptr(), ss.data_ptr()))
+        self.sync()
+        return n.cpu().numpy(), s.cpu().numpy(), ss.cpu().numpy()
+
+    def moments_weighted(self, feat_hwc, wts):
+        """wts [K, h, w] fp32 -> sum [K, C], sumsq [K, C, C]"""
+        h, w, C = feat_hwc.shape
+        K = wts.shape[0]
+        f, wd = self.dev(feat_hwc, np.float32), self.dev(wts, np.float32)
+        s = self.t.empty((K, C), device="cuda", dtype=self.t.float64)
+        ss = self.t.empty((K, C, C), device="cuda", dtype=self.t.float64)
+        self.sync()
+        self.chk(self.L.wct_moments_weighted(self.ctx, f.data_ptr(), C, h, w, wd.data_ptr(), K, s.data_ptr(), ss.data_ptr()))
+        self.sync()
+        return s.cpu().numpy(), ss.cpu().numpy()
+
+    def apply_labeled(self, feat, lab, M, b, nchw=False):
+        """M [K, C, C], b [K, C]"""
+        f, C, h, w, layout = self._layout(feat, nchw)
+        l, Md, bd = self.dev(lab, np.uint8), self.dev(M, np.float64), self.dev(b, np.float64)
+        out = self.t.empty_like(f)
+        self.sync()
+        self.chk(self.L.wct_apply_labeled(self.ctx, f.data_ptr(), C, h, w, layout, l.data_ptr(), M.shape[0], Md.data_ptr(), bd.data_ptr(), out.data_ptr()))
+        self.sync()
+        return out.cpu().numpy()
+
+    def apply_mixed(self, feat, wts, M, b, nchw=False):
+        f, C, h, w, layout = self._layout(feat, nchw)
+        wd, Md, bd = self.dev(wts, np.float32), self.dev(M, np.float64), self.dev(b, np.float64)
+        out = self.t.empty_like(f)
+        self.sync()
+        self.chk(self.L.wct_apply_mixed(self.ctx, f.data_ptr(), C, h, w, layout, wd.data_ptr(), M.shape[0], Md.data_ptr(), bd.data_ptr(), out.data_ptr()))
+        self.sync()
+        return out.cpu().numpy()
+
+    def solve_info(self, C, n_c, s_c, ss_c, n_s, s_s, ss_s, alpha):
+        """solve() that also returns wct_solve's info: how (content, style) were solved"""
+        a = [self.dev(v, np.float64) for v in (s_c, ss_c, s_s, ss_s)]
+        M = self.t.empty(C, C, device="cuda", dtype=self.t.float64)
+        b = self.t.empty(C, device="cuda", dtype=self.t.float64)
+        info = (c_int * 2)(-1, -1)
+        self.sync()
+        self.chk(self.L.wct_solve(self.ctx, C, float(n_c), a[0].data_ptr(), a[1].data_ptr(), float(n_s), a[2].data_ptr(), a[3].data_ptr(),
+                                  float(alpha), M.data_ptr(), b.data_ptr(), info))
+        self.sync()
+        return M.cpu().numpy(), b.cpu().numpy(), (info[0], info[1])
+
+    def transform_solve(self, mode, C, n_c, s_c, ss_c, style_stats, alpha):
+        """mode: "wct" | "ot" | "adain"; style_stats in the wct_style_export layout -> M, b, info"""
+        a = [self.dev(v, np.float64) for v in (s_c, ss_c, style_stats)]
+        M = self.t.empty(C, C, device="cuda", dtype=self.t.float64)
+        b = self.t.empty(C, device="cuda", dtype=self.t.float64)
+        info = (c_int * 2)(-1, -1)
+        self.sync()
+        self.chk(self.L.wct_transform_solve(self.ctx, _lib.TRANSFORMS[mode], C, float(n_c), a[0].data_ptr(), a[1].data_ptr(), a[2].data_ptr(), float(alpha),
+                                            M.data_ptr(), b.data_ptr(), info))
+        self.sync()
+        return M.cpu().numpy(), b.cpu().numpy(), (info[0], info[1])
+
+    def decode_affine(self, level, feat_chw, M, b):
+        C, h, w = feat_chw.shape
+        f = self.dev(feat_chw.transpose(1, 2, 0), np.float32)
+        Md, bd = self.dev(M, np.float64), self.dev(b, np.float64)
+        out = self.t.empty((3, h << (level - 1), w << (level - 1)), device="cuda", dtype=self.t.float32)
+        self.sync()
+        self.chk(self.L.wct_decode_affine(self.ctx, level, f.data_ptr(), h, w, Md.data_ptr(), bd.data_ptr(), out.data_ptr()))
+        self.sync()
+        return out.cpu().numpy()
