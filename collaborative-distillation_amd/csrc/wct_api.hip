@@ -1061,7 +1061,9 @@ int l1_decode_impl(wct_ctx* ctx, int level, const float* img, int H, int W, cons
 
 // style side of one level on the SIDE lane: sF = encoder(styleImg) (WCT.py:100), its moments and eigen-decomposition.
 // Independent of the content, so it is enqueued first and overlaps the content side.  Leaves eigS[level] + ev_style[level].
-int style_side(wct_ctx* ctx, int level, const float* style, int Hs, int Ws) {
+// slot k >= 0 (the K-style calls): into eigR[k][level], and no fold -- their maps are applied to the features or blended into eigS
+// first, not folded into the decoder from here.
+int style_side(wct_ctx* ctx, int level, const float* style, int Hs, int Ws, int slot = -1) {
   Module& me = ctx->mod[WCT_KIND_ENC][level];
   if (!me.loaded) return fail(ctx, WCT_ERR_STATE, "encoder %d not loaded", level);
   const int C = me.layers.back().d.cout;
@@ -1078,8 +1080,10 @@ int style_side(wct_ctx* ctx, int level, const float* style, int Hs, int Ws) {
     if (int rc = encode_impl(ctx, ln, level, style, Hs, Ws, fS, nullptr, nullptr)) return rc;
     if (int rc = moments_impl(ctx, ln, fS, C, hs, ws, 0, ws, sv.sum, sv.sumsq)) return rc;
   }
-  if (int rc = eig_impl(ctx, ln, C, (double)hs * ws, sv.sum, sv.sumsq, 0, ctx->eigS[level], sv.info + 1)) return rc;
-  if (int rc = style_fold(ctx, level, ln.stream)) return rc;      // (W Ss), off the content side's critical path
+  DevBuf& res = slot < 0 ? ctx->eigS[level] : ctx->eigR[slot][level];
+  if (int rc = eig_impl(ctx, ln, C, (double)hs * ws, sv.sum, sv.sumsq, 0, res, sv.info + 1)) return rc;
+  if (slot < 0)
+    if (int rc = style_fold(ctx, level, ln.stream)) return rc;    // (W Ss), off the content side's critical path
   HIPCHK(ctx, hipEventRecord(ctx->ev_style[level], ln.stream));
   return WCT_OK;
 }
@@ -1132,6 +1136,44 @@ int content_side(wct_ctx* ctx, int level, const float* content, int H, int W, fl
   }
   if (Ho) *Ho = h << (level - 1);
   if (Wo) *Wo = w << (level - 1);
+  return WCT_OK;
+}
+
+// The five levels 5..1 of WCT.py:120-125, num_run times over.  `out` doubles as the running image: level L reads one buffer and
+// writes the other (ping-pong with tmpT), the parity chosen so that the last level writes into `out`.
+//   level_fn(level, cur, h, w, dst, &ho, &wo): level L of the h x w image `cur` into `dst`, ho x wo
+//   after_level(level): in the first run behind every level L > 1 -- where a caller enqueues the style side of level L - 1
+// Deferred solves and the range read-back stay with the caller: the entry points place them differently.
+template <typename LEVEL, typename AFTER>
+int run_cascade(wct_ctx* ctx, const float* content, int H, int W, int num_run, float* out, int* Ho, int* Wo, LEVEL&& level_fn, AFTER&& after_level) {
+  if (int rc = ensure(ctx, ctx->tmpT, (size_t)3 * H * W * sizeof(float))) return rc;
+  float* bufs[2] = {reinterpret_cast<float*>(ctx->tmpT.p), out};
+  const float* cur = content;
+  int h = H, w = W, which = (5 * num_run) & 1;
+  for (int run = 0; run < num_run; ++run)
+    for (int level = 5; level >= 1; --level) {
+      int ho = 0, wo = 0;
+      float* dst = bufs[which];
+      if (int rc = level_fn(level, cur, h, w, dst, &ho, &wo)) return rc;
+      if (run == 0 && level > 1)
+        if (int rc = after_level(level)) return rc;
+      cur = dst; h = ho; w = wo; which ^= 1;
+    }
+  if (cur != out) HIPCHK(ctx, hipMemcpyAsync(out, cur, (size_t)3 * h * w * sizeof(float), hipMemcpyDeviceToDevice, ctx->main.stream));
+  if (Ho) *Ho = h;
+  if (Wo) *Wo = w;
+  return WCT_OK;
+}
+
+// an NHWC map operation apply_nhwc(in, out) on an NCHW map of npix pixels: transposed through the two halves of tmpT
+template <typename APPLY>
+int apply_nchw(wct_ctx* ctx, const float* feat, int C, long npix, float* out, APPLY&& apply_nhwc) {
+  if (int rc = ensure(ctx, ctx->tmpT, 2 * (size_t)npix * C * sizeof(float))) return rc;
+  float* t0 = reinterpret_cast<float*>(ctx->tmpT.p);
+  float* t1 = t0 + (size_t)npix * C;
+  HIPCHK(ctx, launch_nchw_to_nhwc(feat, t0, C, (int)npix, ctx->main.stream));
+  if (int rc = apply_nhwc(t0, t1)) return rc;
+  HIPCHK(ctx, launch_nhwc_to_nchw(t1, out, C, (int)npix, ctx->main.stream));
   return WCT_OK;
 }
 
@@ -1575,7 +1617,6 @@ int wct_apply(wct_ctx* ctx, const float* feat, int C, int h, int w, int layout, 
   if (!feat || !M || !b || !out || h < 2 || w < 2 || C < 4 || (C & 3) || C > 512) return fail(ctx, WCT_ERR_INVALID, "apply: bad arguments");
   const int cp = pad_cout(C), chunks = (C + 15) / 16;
   const size_t wfl = (size_t)chunks * 36 * cp * 4;
-  const size_t fbytes = (size_t)h * w * C * sizeof(float);
   if (int rc = ensure(ctx, ctx->foldW, (wfl + cp) * sizeof(float))) return rc;
   float* wpk = reinterpret_cast<float*>(ctx->foldW.p);
   float* bias = wpk + wfl;
@@ -1584,13 +1625,7 @@ int wct_apply(wct_ctx* ctx, const float* feat, int C, int h, int w, int layout, 
   d.cin = C; d.cout = C; d.cin_chunks = chunks; d.cout_pad = cp; d.flags = CONV_NO_RELU; d.wpk = wpk; d.bias = bias;
   if (layout == WCT_LAYOUT_NHWC) return run_conv(ctx, ctx->main, d, feat, out, h, w);
   if (layout != WCT_LAYOUT_NCHW) return fail(ctx, WCT_ERR_INVALID, "apply: bad layout %d", layout);
-  if (int rc = ensure(ctx, ctx->tmpT, 2 * fbytes)) return rc;
-  float* t0 = reinterpret_cast<float*>(ctx->tmpT.p);
-  float* t1 = t0 + (size_t)h * w * C;
-  HIPCHK(ctx, launch_nchw_to_nhwc(feat, t0, C, h * w, ctx->main.stream));
-  if (int rc = run_conv(ctx, ctx->main, d, t0, t1, h, w)) return rc;
-  HIPCHK(ctx, launch_nhwc_to_nchw(t1, out, C, h * w, ctx->main.stream));
-  return WCT_OK;
+  return apply_nchw(ctx, feat, C, (long)h * w, out, [&](const float* in, float* res) { return run_conv(ctx, ctx->main, d, in, res, h, w); });
 }
 
 int wct_transform(wct_ctx* ctx, const float* cF, int C, int h, int w, const float* sF, int hs, int ws, float alpha,
@@ -1907,29 +1942,12 @@ namespace {
 // `style` (wct_stylize): the style side of level L - 1 is enqueued behind the content side of level L of the first run
 int cascade(wct_ctx* ctx, const float* content, int H, int W, float alpha, int num_run, float* out, int* Ho, int* Wo,
             const float* style = nullptr, int Hs = 0, int Ws = 0) {
-  // `out` doubles as the running image: level L reads one buffer and writes the other (ping-pong with tmpT)
-  const size_t img_bytes = (size_t)3 * H * W * sizeof(float);
-  if (int rc = ensure(ctx, ctx->tmpT, img_bytes)) return rc;
-  float* bufs[2] = {reinterpret_cast<float*>(ctx->tmpT.p), out};
-  const float* cur = content;
-  int h = H, w = W, which = (5 * num_run) & 1;  // so that the last level writes into `out`
-  for (int run = 0; run < num_run; ++run)
-    for (int level = 5; level >= 1; --level) {
-      int ho, wo;
-      float* dst = bufs[which];
-      if (int rc = content_side(ctx, level, cur, h, w, alpha, dst, &ho, &wo)) return rc;
-      if (style && run == 0 && level > 1)
-        if (int rc = style_side(ctx, level - 1, style, Hs, Ws)) return rc;
-      cur = dst; h = ho; w = wo; which ^= 1;
-    }
-  if (cur != out) HIPCHK(ctx, hipMemcpyAsync(out, cur, (size_t)3 * h * w * sizeof(float), hipMemcpyDeviceToDevice, ctx->main.stream));
-  if (Ho) *Ho = h;
-  if (Wo) *Wo = w;
+  if (int rc = run_cascade(ctx, content, H, W, num_run, out, Ho, Wo,
+        [&](int level, const float* cur, int h, int w, float* dst, int* ho, int* wo) { return content_side(ctx, level, cur, h, w, alpha, dst, ho, wo); },
+        [&](int level) { return style ? style_side(ctx, level - 1, style, Hs, Ws) : (int)WCT_OK; })) return rc;
   return range_readback(ctx);
 }
-}  // namespace
 
-namespace {
 // the bodies of wct_stylize / wct_stylize_prepared behind their argument checks; wct_synthesize runs them on its noise image
 int stylize_impl(wct_ctx* ctx, const float* content, int H, int W, const float* style, int Hs, int Ws, float alpha, int num_run, float* out,
                  int* Ho, int* Wo) {
@@ -2111,39 +2129,6 @@ int wct_luma_merge(wct_ctx* ctx, const float* stylised, int Ho, int Wo, const fl
   return luma_merge_impl(ctx, stylised, Ho, Wo, content, Hc, Wc, out_planar, out_hwc, round_mode);
 }
 
-int wct_stylize_color(wct_ctx* ctx, const float* content, int H, int W, const float* style, int Hs, int Ws, float alpha, int num_run, int mode,
-                      float* out, int* Ho, int* Wo) {
-  if (!ctx) return WCT_ERR_INVALID;
-  WCT_GUARD(ctx);
-  if (!content || !style || !out || num_run < 1) return fail(ctx, WCT_ERR_INVALID, "wct_stylize_color: bad arguments (a NULL pointer, or num_run < 1)");
-  if (mode < 1 || mode > 3)
-    return fail(ctx, WCT_ERR_INVALID, "wct_stylize_color: mode %d is not WCT_COLOR_MATCH (1), WCT_COLOR_LUMA (2) or both (3)", mode);
-  if (H < 1 || W < 1 || Hs < 1 || Ws < 1 || ((mode & WCT_COLOR_MATCH) && ((long)Hs * Ws < 2 || (long)H * W < 2)))
-    return fail(ctx, WCT_ERR_INVALID, "wct_stylize_color: bad shapes (content %dx%d, style %dx%d)", H, W, Hs, Ws);
-  if ((mode & WCT_COLOR_MATCH) && ((long)Hs * Ws > color_moments_max_pixels() || (long)H * W > color_moments_max_pixels()))
-    return fail(ctx, WCT_ERR_INVALID, "wct_stylize_color: style %dx%d or content %dx%d exceeds the %ld pixels the summation contract covers", Hs, Ws, H, W,
-                color_moments_max_pixels());
-  // every buffer first: a growing one synchronises, and nothing enqueued below may find its source moved
-  if (mode & WCT_COLOR_MATCH)
-    if (int rc = ensure(ctx, ctx->colStyle, (size_t)3 * Hs * Ws * sizeof(float))) return rc;
-  if (mode & WCT_COLOR_LUMA)
-    if (int rc = ensure(ctx, ctx->colOut, (size_t)3 * H * W * sizeof(float))) return rc;
-  const float* st = style;
-  if (mode & WCT_COLOR_MATCH) {
-    float* matched = reinterpret_cast<float*>(ctx->colStyle.p);
-    if (int rc = color_match_impl(ctx, style, Hs, Ws, content, H, W, matched)) return rc;
-    st = matched;   // the side lane reads it behind fork_side's event, and the cascade's last level has waited for the side lane
-  }
-  float* dst = (mode & WCT_COLOR_LUMA) ? reinterpret_cast<float*>(ctx->colOut.p) : out;
-  int ho = 0, wo = 0;
-  if (int rc = stylize_impl(ctx, content, H, W, st, Hs, Ws, alpha, num_run, dst, &ho, &wo)) return rc;
-  if (mode & WCT_COLOR_LUMA)
-    if (int rc = luma_merge_impl(ctx, dst, ho, wo, content, H, W, out, nullptr, 0)) return rc;
-  if (Ho) *Ho = ho;
-  if (Wo) *Wo = wo;
-  return WCT_OK;
-}
-
 // ---- guided-filter smoothing (include/wct_hip_smooth.h; kernels in smooth.hip) -------------------------------------------------------
 namespace {
 int smooth_bufs(wct_ctx* ctx, long npix) {
@@ -2173,6 +2158,50 @@ bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
   const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
   return a0 < b0 + nb && b0 < a0 + na;
 }
+
+// body of wct_stylize_color and wct_stylize_smooth (`who`): colour match -> stylize -> [guided filter by the content] -> [luma merge].
+// `smooth`: the filter runs, (radius, eps) are checked, and mode 0 (no colour preservation) is allowed.
+int stylize_color_impl(wct_ctx* ctx, const char* who, bool smooth, const float* content, int H, int W, const float* style, int Hs, int Ws, float alpha,
+                       int num_run, int mode, int radius, double eps, float* out, int* Ho, int* Wo) {
+  if (!content || !style || !out || num_run < 1) return fail(ctx, WCT_ERR_INVALID, "%s: bad arguments (a NULL pointer, or num_run < 1)", who);
+  if (mode < (smooth ? 0 : 1) || mode > 3)
+    return fail(ctx, WCT_ERR_INVALID, "%s: %s %d is not %sWCT_COLOR_MATCH (1), WCT_COLOR_LUMA (2) or both (3)", who, smooth ? "color_mode" : "mode", mode,
+                smooth ? "0, " : "");
+  const bool match = mode & WCT_COLOR_MATCH, luma = mode & WCT_COLOR_LUMA;
+  if (H < 1 || W < 1 || Hs < 1 || Ws < 1 || (match && ((long)Hs * Ws < 2 || (long)H * W < 2)))
+    return fail(ctx, WCT_ERR_INVALID, "%s: bad shapes (content %dx%d, style %dx%d)", who, H, W, Hs, Ws);
+  if (match && ((long)Hs * Ws > color_moments_max_pixels() || (long)H * W > color_moments_max_pixels()))
+    return fail(ctx, WCT_ERR_INVALID, "%s: style %dx%d or content %dx%d exceeds the %ld pixels the summation contract covers", who, Hs, Ws, H, W,
+                color_moments_max_pixels());
+  if (smooth) {
+    if (int rc = smooth_check(ctx, who, radius, eps)) return rc;
+    if (ranges_overlap(out, (size_t)3 * H * W * sizeof(float), content, (size_t)3 * H * W * sizeof(float)))
+      return fail(ctx, WCT_ERR_INVALID, "%s: out overlaps the content, which is the filter's guide", who);
+  }
+  // every buffer first: a growing one synchronises, and nothing enqueued below may find its source moved
+  if (match)
+    if (int rc = ensure(ctx, ctx->colStyle, (size_t)3 * Hs * Ws * sizeof(float))) return rc;
+  if (luma)
+    if (int rc = ensure(ctx, ctx->colOut, (size_t)3 * H * W * sizeof(float))) return rc;
+  if (smooth)
+    if (int rc = smooth_bufs(ctx, (long)H * W)) return rc;   // the result is no larger than the content
+  const float* st = style;
+  if (match) {
+    float* matched = reinterpret_cast<float*>(ctx->colStyle.p);
+    if (int rc = color_match_impl(ctx, style, Hs, Ws, content, H, W, matched)) return rc;
+    st = matched;   // the side lane reads it behind fork_side's event, and the cascade's last level has waited for the side lane
+  }
+  float* dst = luma ? reinterpret_cast<float*>(ctx->colOut.p) : out;
+  int ho = 0, wo = 0;
+  if (int rc = stylize_impl(ctx, content, H, W, st, Hs, Ws, alpha, num_run, dst, &ho, &wo)) return rc;
+  if (smooth)
+    if (int rc = guided_filter_impl(ctx, dst, ho, wo, content, H, W, radius, eps, dst, nullptr, 0)) return rc;   // in place
+  if (luma)
+    if (int rc = luma_merge_impl(ctx, dst, ho, wo, content, H, W, out, nullptr, 0)) return rc;
+  if (Ho) *Ho = ho;
+  if (Wo) *Wo = wo;
+  return WCT_OK;
+}
 }  // namespace
 
 int wct_guided_filter(wct_ctx* ctx, const float* src, int Ho, int Wo, const float* guide, int Hg, int Wg, int radius, double eps, float* out_planar,
@@ -2193,43 +2222,19 @@ int wct_guided_filter(wct_ctx* ctx, const float* src, int Ho, int Wo, const floa
   return guided_filter_impl(ctx, src, Ho, Wo, guide, Hg, Wg, radius, eps, out_planar, out_hwc, round_mode);
 }
 
+// (include/wct_hip_color.h; here because it shares its body with wct_stylize_smooth)
+int wct_stylize_color(wct_ctx* ctx, const float* content, int H, int W, const float* style, int Hs, int Ws, float alpha, int num_run, int mode,
+                      float* out, int* Ho, int* Wo) {
+  if (!ctx) return WCT_ERR_INVALID;
+  WCT_GUARD(ctx);
+  return stylize_color_impl(ctx, "wct_stylize_color", false, content, H, W, style, Hs, Ws, alpha, num_run, mode, 0, 0., out, Ho, Wo);
+}
+
 int wct_stylize_smooth(wct_ctx* ctx, const float* content, int H, int W, const float* style, int Hs, int Ws, float alpha, int num_run, int color_mode,
                        int radius, double eps, float* out, int* Ho, int* Wo) {
   if (!ctx) return WCT_ERR_INVALID;
   WCT_GUARD(ctx);
-  if (!content || !style || !out || num_run < 1) return fail(ctx, WCT_ERR_INVALID, "wct_stylize_smooth: bad arguments (a NULL pointer, or num_run < 1)");
-  if (color_mode < 0 || color_mode > 3)
-    return fail(ctx, WCT_ERR_INVALID, "wct_stylize_smooth: color_mode %d is not 0, WCT_COLOR_MATCH (1), WCT_COLOR_LUMA (2) or both (3)", color_mode);
-  const bool match = color_mode & WCT_COLOR_MATCH, luma = color_mode & WCT_COLOR_LUMA;
-  if (H < 1 || W < 1 || Hs < 1 || Ws < 1 || (match && ((long)Hs * Ws < 2 || (long)H * W < 2)))
-    return fail(ctx, WCT_ERR_INVALID, "wct_stylize_smooth: bad shapes (content %dx%d, style %dx%d)", H, W, Hs, Ws);
-  if (match && ((long)Hs * Ws > color_moments_max_pixels() || (long)H * W > color_moments_max_pixels()))
-    return fail(ctx, WCT_ERR_INVALID, "wct_stylize_smooth: style %dx%d or content %dx%d exceeds the %ld pixels the summation contract covers", Hs, Ws, H, W,
-                color_moments_max_pixels());
-  if (int rc = smooth_check(ctx, "wct_stylize_smooth", radius, eps)) return rc;
-  if (ranges_overlap(out, (size_t)3 * H * W * sizeof(float), content, (size_t)3 * H * W * sizeof(float)))
-    return fail(ctx, WCT_ERR_INVALID, "wct_stylize_smooth: out overlaps the content, which is the filter's guide");
-  // every buffer first: a growing one synchronises, and nothing enqueued below may find its source moved
-  if (match)
-    if (int rc = ensure(ctx, ctx->colStyle, (size_t)3 * Hs * Ws * sizeof(float))) return rc;
-  if (luma)
-    if (int rc = ensure(ctx, ctx->colOut, (size_t)3 * H * W * sizeof(float))) return rc;
-  if (int rc = smooth_bufs(ctx, (long)H * W)) return rc;   // the result is no larger than the content
-  const float* st = style;
-  if (match) {
-    float* matched = reinterpret_cast<float*>(ctx->colStyle.p);
-    if (int rc = color_match_impl(ctx, style, Hs, Ws, content, H, W, matched)) return rc;
-    st = matched;
-  }
-  float* dst = luma ? reinterpret_cast<float*>(ctx->colOut.p) : out;
-  int ho = 0, wo = 0;
-  if (int rc = stylize_impl(ctx, content, H, W, st, Hs, Ws, alpha, num_run, dst, &ho, &wo)) return rc;
-  if (int rc = guided_filter_impl(ctx, dst, ho, wo, content, H, W, radius, eps, dst, nullptr, 0)) return rc;   // in place
-  if (luma)
-    if (int rc = luma_merge_impl(ctx, dst, ho, wo, content, H, W, out, nullptr, 0)) return rc;
-  if (Ho) *Ho = ho;
-  if (Wo) *Wo = wo;
-  return WCT_OK;
+  return stylize_color_impl(ctx, "wct_stylize_smooth", true, content, H, W, style, Hs, Ws, alpha, num_run, color_mode, radius, eps, out, Ho, Wo);
 }
 
 int wct_u8_to_planar(wct_ctx* ctx, const uint8_t* hwc, int H, int W, float* planar) {
@@ -2587,67 +2592,73 @@ int apply_labeled_impl(wct_ctx* ctx, const float* feat, int C, long npix, const 
   return WCT_OK;
 }
 
-// style side of one level for style slot k (the same steps as style_side, into eigR[k][level]; no fold: the regions' maps are applied
-// to the features, not folded into the decoder)
-int style_side_slot(wct_ctx* ctx, int level, int k, const float* style, int Hs, int Ws) {
-  Module& me = ctx->mod[WCT_KIND_ENC][level];
-  if (!me.loaded) return fail(ctx, WCT_ERR_STATE, "encoder %d not loaded", level);
-  const int C = me.layers.back().d.cout;
-  int hs, ws;
-  level_dims(level, Hs, Ws, hs, ws);
-  Lane& ln = ctx->overlap ? ctx->side : ctx->main;
-  if (int rc = ensure(ctx, ctx->featS, (size_t)hs * ws * C * sizeof(float))) return rc;
-  SumsView sv;
-  if (int rc = sums_view(ctx, ln, sv)) return rc;
-  float* fS = reinterpret_cast<float*>(ctx->featS.p);
-  if (l1_fused(ctx, level)) {
-    if (int rc = l1_moments_impl(ctx, ln, level, style, Hs, Ws, 0, Ws, sv.sum, sv.sumsq)) return rc;
-  } else {
-    if (int rc = encode_impl(ctx, ln, level, style, Hs, Ws, fS, nullptr, nullptr)) return rc;
-    if (int rc = moments_impl(ctx, ln, fS, C, hs, ws, 0, ws, sv.sum, sv.sumsq)) return rc;
-  }
-  if (int rc = eig_impl(ctx, ln, C, (double)hs * ws, sv.sum, sv.sumsq, 0, ctx->eigR[k][level], sv.info + 1)) return rc;
-  HIPCHK(ctx, hipEventRecord(ctx->ev_style[level], ln.stream));
+// the K style sides of one level, slot by slot (they share featS and the side lane's sums: one after the other)
+int style_side_slots(wct_ctx* ctx, int level, int K, const float* const* styles, const int* Hs, const int* Ws) {
+  for (int k = 0; k < K; ++k)
+    if (int rc = style_side(ctx, level, styles[k], Hs[k], Ws[k], k)) return rc;
   return WCT_OK;
 }
 
-// geometry of a regions call: level L's feature map is h[L] x w[L] in every run (the cascade crops to multiples of 16 at level 5 and
-// keeps that size), its label map lives at regLab + off[L]; cnt[L][v] = pixels of lab_L with label v (host, read back once)
-struct RegionPlan {
+// geometry of a K-style call: level L's feature map is h[L] x w[L] in every run (the cascade crops to multiples of 16 at level 5 and
+// keeps that size); what the call keeps per level (label map, K pooled weight maps) lives at element off[L] of its buffer
+struct LevelGeom {
   int h[6], w[6];
   size_t off[6];
+};
+
+// g for an H x W content with per_pixel elements per feature pixel, every level's block padded to a multiple of `align` elements (a
+// power of two); returns the elements of all five
+size_t level_geom(LevelGeom& g, int H, int W, size_t per_pixel, size_t align) {
+  size_t total = 0;
+  for (int level = 5; level >= 1; --level) {
+    g.h[level] = (H >> 4) << (5 - level);
+    g.w[level] = (W >> 4) << (5 - level);
+    g.off[level] = total;
+    total += (per_pixel * g.h[level] * g.w[level] + align - 1) & ~(align - 1);
+  }
+  return total;
+}
+
+// a regions call: the level label maps in regLab (bytes); cnt[L][v] = pixels of lab_L with label v (host, read back once)
+struct RegionPlan : LevelGeom {
   unsigned cnt[6][256];
 };
 
-// one level of the regions cascade on the main lane: encoder (fp32 NHWC) -> per-label moments -> one content solve per region with
-// >= 2 pixels, against style slot k -> per-label apply -> the decoder with its unfolded first conv
-int regions_level(wct_ctx* ctx, int level, const float* img, int H, int W, const RegionPlan& pl, int K, const float* alpha, float* dst) {
+// One level of a K-style cascade on the main lane: encoder (fp32 NHWC) -> K sets of content moments -> one content solve per active
+// slot k, against style slot k -> (M, b) per slot, the identity for the idle ones -> apply -> the decoder with its unfolded first conv.
+// What the regions and the weights cascades do differently comes in as callables:
+//   moments(fC, C, h, w, n, sum, sumsq): the K moment sets into regSums = [n K (only with n_head) |] sum K*C | sumsq K*C*C
+//   slot_n(k): the samples behind slot k's moments, as the solver is to count them; below 2 the slot is idle
+//   apply(fC, C, npix, M, b, fO): the K maps on the feature
+// `what` names the cascade in the refusal.
+template <typename MOMENTS, typename SLOTN, typename APPLY>
+int multi_style_level(wct_ctx* ctx, const char* what, int level, const float* img, int H, int W, const LevelGeom& g, int K, const float* alpha,
+                      bool n_head, float* dst, int* ho, int* wo, MOMENTS&& moments, SLOTN&& slot_n, APPLY&& apply) {
   Module& me = ctx->mod[WCT_KIND_ENC][level];
   const int C = me.layers.back().d.cout;
   int h, w;
   level_dims(level, H, W, h, w);
-  if (h != pl.h[level] || w != pl.w[level]) return fail(ctx, WCT_ERR_INVALID, "regions: level %d map %dx%d, planned %dx%d", level, h, w, pl.h[level], pl.w[level]);
+  if (h != g.h[level] || w != g.w[level]) return fail(ctx, WCT_ERR_INVALID, "%s: level %d map %dx%d, planned %dx%d", what, level, h, w, g.h[level], g.w[level]);
   Lane& ln = ctx->main;
   const size_t fbytes = (size_t)h * w * C * sizeof(float), cc = (size_t)C * C;
   if (int rc = ensure(ctx, ctx->featC, fbytes)) return rc;
   if (int rc = ensure(ctx, ctx->regFeat, fbytes)) return rc;
-  if (int rc = ensure(ctx, ctx->regSums, (size_t)K * (1 + C + cc) * sizeof(double))) return rc;
+  if (int rc = ensure(ctx, ctx->regSums, (size_t)K * ((n_head ? 1 : 0) + C + cc) * sizeof(double))) return rc;
   if (int rc = ensure(ctx, ctx->regMb, (size_t)K * (cc + C) * sizeof(double))) return rc;
   SumsView sv;
   if (int rc = sums_view(ctx, ln, sv)) return rc;
   float* fC = reinterpret_cast<float*>(ctx->featC.p);
   float* fO = reinterpret_cast<float*>(ctx->regFeat.p);
   double* n = reinterpret_cast<double*>(ctx->regSums.p);
-  double* sum = n + K;
+  double* sum = n + (n_head ? K : 0);
   double* sumsq = sum + (size_t)K * C;
   double* M = reinterpret_cast<double*>(ctx->regMb.p);
   double* b = M + (size_t)K * cc;
-  const uint8_t* lab = reinterpret_cast<const uint8_t*>(ctx->regLab.p) + pl.off[level];
   if (int rc = encode_impl(ctx, ln, level, img, H, W, fC, nullptr, nullptr)) return rc;
-  if (int rc = moments_labeled_impl(ctx, ln, fC, C, h, w, lab, K, n, sum, sumsq)) return rc;
+  if (int rc = moments(fC, C, h, w, n, sum, sumsq)) return rc;
   unsigned ident = 0;
   for (int k = 0; k < K; ++k) {
-    const double nk = pl.cnt[level][k];
+    const double nk = slot_n(k);
     if (nk < 2) { ident |= 1u << k; continue; }
     if (int rc = eig_impl(ctx, ln, C, nk, sum + (size_t)k * C, sumsq + k * cc, 1, ctx->eigCR[k], sv.info)) return rc;
   }
@@ -2656,8 +2667,23 @@ int regions_level(wct_ctx* ctx, int level, const float* img, int H, int W, const
     if (!(ident >> k & 1u))
       if (int rc = assemble_impl(ctx, C, ctx->eigCR[k], ctx->eigR[k][level], alpha[k], M + k * cc, b + (size_t)k * C)) return rc;
   HIPCHK(ctx, launch_mb_identity(M, b, C, K, ident, ln.stream));
-  if (int rc = apply_labeled_impl(ctx, fC, C, (long)h * w, lab, K, M, b, fO)) return rc;
-  return decode_impl(ctx, level, fO, h, w, nullptr, dst);
+  if (int rc = apply(fC, C, (long)h * w, M, b, fO)) return rc;
+  if (int rc = decode_impl(ctx, level, fO, h, w, nullptr, dst)) return rc;
+  *ho = h << (level - 1);
+  *wo = w << (level - 1);
+  return WCT_OK;
+}
+
+// one level of the regions cascade: per-label moments, a region with fewer than 2 pixels keeps its features, per-label apply
+int regions_level(wct_ctx* ctx, int level, const float* img, int H, int W, const RegionPlan& pl, int K, const float* alpha, float* dst, int* ho, int* wo) {
+  const uint8_t* lab = reinterpret_cast<const uint8_t*>(ctx->regLab.p) + pl.off[level];
+  return multi_style_level(
+      ctx, "regions", level, img, H, W, pl, K, alpha, true, dst, ho, wo,
+      [&](const float* fC, int C, int h, int w, double* n, double* sum, double* sumsq) {
+        return moments_labeled_impl(ctx, ctx->main, fC, C, h, w, lab, K, n, sum, sumsq);
+      },
+      [&](int k) -> double { return pl.cnt[level][k]; },
+      [&](const float* fC, int C, long npix, const double* M, const double* b, float* fO) { return apply_labeled_impl(ctx, fC, C, npix, lab, K, M, b, fO); });
 }
 }  // namespace
 
@@ -2681,14 +2707,7 @@ int wct_apply_labeled(wct_ctx* ctx, const float* feat, int C, int h, int w, int 
   const long npix = (long)h * w;
   if (layout == WCT_LAYOUT_NHWC) return apply_labeled_impl(ctx, feat, C, npix, lab, K, M, b, out);
   if (layout != WCT_LAYOUT_NCHW) return fail(ctx, WCT_ERR_INVALID, "apply_labeled: bad layout %d", layout);
-  const size_t fbytes = (size_t)npix * C * sizeof(float);
-  if (int rc = ensure(ctx, ctx->tmpT, 2 * fbytes)) return rc;
-  float* t0 = reinterpret_cast<float*>(ctx->tmpT.p);
-  float* t1 = t0 + (size_t)npix * C;
-  HIPCHK(ctx, launch_nchw_to_nhwc(feat, t0, C, (int)npix, ctx->main.stream));
-  if (int rc = apply_labeled_impl(ctx, t0, C, npix, lab, K, M, b, t1)) return rc;
-  HIPCHK(ctx, launch_nhwc_to_nchw(t1, out, C, (int)npix, ctx->main.stream));
-  return WCT_OK;
+  return apply_nchw(ctx, feat, C, npix, out, [&](const float* in, float* res) { return apply_labeled_impl(ctx, in, C, npix, lab, K, M, b, res); });
 }
 
 int wct_stylize_regions(wct_ctx* ctx, const float* content, int H, int W, const uint8_t* labels, int K, const float* const* styles,
@@ -2708,13 +2727,7 @@ int wct_stylize_regions(wct_ctx* ctx, const float* content, int H, int W, const 
   // label maps of the five levels + their histograms, read back ONCE: the solvers take each region's pixel count on the host, and the
   // labels are checked before anything is written to `out`
   RegionPlan pl{};
-  size_t total = 0;
-  for (int level = 5; level >= 1; --level) {
-    pl.h[level] = (H >> 4) << (5 - level);
-    pl.w[level] = (W >> 4) << (5 - level);
-    pl.off[level] = total;
-    total += ((size_t)pl.h[level] * pl.w[level] + 255) & ~(size_t)255;
-  }
+  const size_t total = level_geom(pl, H, W, 1, 256);
   if (int rc = ensure(ctx, ctx->regLab, total)) return rc;
   if (int rc = ensure(ctx, ctx->regHist, 6 * 256 * sizeof(unsigned))) return rc;
   if (!ctx->reg_hist_host) HIPCHK(ctx, hipHostMalloc(reinterpret_cast<void**>(&ctx->reg_hist_host), 6 * 256 * sizeof(unsigned), hipHostMallocDefault));
@@ -2733,28 +2746,11 @@ int wct_stylize_regions(wct_ctx* ctx, const float* content, int H, int W, const 
       return fail(ctx, WCT_ERR_INVALID, "stylize_regions: label value %d (%u pixels) is neither a region 0..%d nor 255 (unstyled)", v, pl.cnt[0][v], K - 1);
   if (int rc = with_deferred_solves(ctx, false, [&]() -> int {
         if (int rc = fork_side(ctx)) return rc;
-        for (int k = 0; k < K; ++k)
-          if (int rc = style_side_slot(ctx, 5, k, styles[k], Hs[k], Ws[k])) return rc;
-        // as cascade(): `out` doubles as the running image; the style slots of level L - 1 are enqueued behind level L's content side
-        const size_t img_bytes = (size_t)3 * H * W * sizeof(float);
-        if (int rc = ensure(ctx, ctx->tmpT, img_bytes)) return rc;
-        float* bufs[2] = {reinterpret_cast<float*>(ctx->tmpT.p), out};
-        const float* cur = content;
-        int h = H, w = W, which = (5 * num_run) & 1;
-        for (int run = 0; run < num_run; ++run)
-          for (int level = 5; level >= 1; --level) {
-            float* dst = bufs[which];
-            if (int rc = regions_level(ctx, level, cur, h, w, pl, K, alpha, dst)) return rc;
-            if (run == 0 && level > 1)
-              for (int k = 0; k < K; ++k)
-                if (int rc = style_side_slot(ctx, level - 1, k, styles[k], Hs[k], Ws[k])) return rc;
-            h = pl.h[level] << (level - 1); w = pl.w[level] << (level - 1);
-            cur = dst; which ^= 1;
-          }
-        if (cur != out) HIPCHK(ctx, hipMemcpyAsync(out, cur, (size_t)3 * h * w * sizeof(float), hipMemcpyDeviceToDevice, ctx->main.stream));
-        if (Ho) *Ho = h;
-        if (Wo) *Wo = w;
-        return WCT_OK;
+        if (int rc = style_side_slots(ctx, 5, K, styles, Hs, Ws)) return rc;
+        return run_cascade(
+            ctx, content, H, W, num_run, out, Ho, Wo,
+            [&](int level, const float* cur, int h, int w, float* dst, int* ho, int* wo) { return regions_level(ctx, level, cur, h, w, pl, K, alpha, dst, ho, wo); },
+            [&](int level) { return style_side_slots(ctx, level - 1, K, styles, Hs, Ws); });
       })) return rc;
   return range_readback(ctx);
 }
@@ -2812,8 +2808,7 @@ int blend_into_style(wct_ctx* ctx, int level, int K, const double* const* F, con
 
 // style side of one level of wct_stylize_interp: the K style sides into eigR[k][level], then their blend into eigS[level] (side lane)
 int interp_style_side(wct_ctx* ctx, int level, int K, const float* const* styles, const int* Hs, const int* Ws, const double* lam) {
-  for (int k = 0; k < K; ++k)
-    if (int rc = style_side_slot(ctx, level, k, styles[k], Hs[k], Ws[k])) return rc;
+  if (int rc = style_side_slots(ctx, level, K, styles, Hs, Ws)) return rc;
   const size_t C = ctx->mod[WCT_KIND_ENC][level].layers.back().d.cout, cc = C * C;
   const double* F[REG_MAX];
   const double* mu[REG_MAX];
@@ -2838,62 +2833,30 @@ int multi_style_args(wct_ctx* ctx, const char* what, const float* content, int H
   return WCT_OK;
 }
 
-// geometry of a weights call (as RegionPlan): level L's map is h[L] x w[L], its K pooled weight maps live at blendW + off[L] (floats);
-// V1[L][k], V2[L][k] read back once
-struct BlendPlan {
-  int h[6], w[6];
-  size_t off[6];
+// a weights call: the K pooled weight maps of every level in blendW (floats); V1[L][k], V2[L][k] read back once
+struct BlendPlan : LevelGeom {
   double V1[6][REG_MAX], V2[6][REG_MAX];
 };
 constexpr size_t BLEND_STAT_BYTES = 6 * REG_MAX * 2 * sizeof(double) + 4 * sizeof(unsigned);
 
-// one level of the weights cascade on the main lane: encoder (fp32 NHWC) -> weighted moments -> one content solve per active k (n_eff =
-// V1^2 / V2 with sums scaled by V1 / V2: the solver's (sumsq - n mu mu^T) / (n - 1) is then the reliability-weighted covariance) ->
-// mixed apply -> the decoder with its unfolded first conv
-int blend_level(wct_ctx* ctx, int level, const float* img, int H, int W, const BlendPlan& pl, int K, const float* alpha, float* dst) {
-  Module& me = ctx->mod[WCT_KIND_ENC][level];
-  const int C = me.layers.back().d.cout;
-  int h, w;
-  level_dims(level, H, W, h, w);
-  if (h != pl.h[level] || w != pl.w[level]) return fail(ctx, WCT_ERR_INVALID, "stylize_blend: level %d map %dx%d, planned %dx%d", level, h, w, pl.h[level], pl.w[level]);
-  Lane& ln = ctx->main;
-  const size_t fbytes = (size_t)h * w * C * sizeof(float), cc = (size_t)C * C;
-  if (int rc = ensure(ctx, ctx->featC, fbytes)) return rc;
-  if (int rc = ensure(ctx, ctx->regFeat, fbytes)) return rc;
-  if (int rc = ensure(ctx, ctx->regSums, (size_t)K * (C + cc) * sizeof(double))) return rc;
-  if (int rc = ensure(ctx, ctx->regMb, (size_t)K * (cc + C) * sizeof(double))) return rc;
-  SumsView sv;
-  if (int rc = sums_view(ctx, ln, sv)) return rc;
-  float* fC = reinterpret_cast<float*>(ctx->featC.p);
-  float* fO = reinterpret_cast<float*>(ctx->regFeat.p);
-  double* sum = reinterpret_cast<double*>(ctx->regSums.p);
-  double* sumsq = sum + (size_t)K * C;
-  double* M = reinterpret_cast<double*>(ctx->regMb.p);
-  double* b = M + (size_t)K * cc;
+// one level of the weights cascade: weighted moments, n_eff = V1^2 / V2 samples per active style with its sums scaled by V1 / V2 (the
+// solver's (sumsq - n mu mu^T) / (n - 1) is then the reliability-weighted covariance), mixed apply
+int blend_level(wct_ctx* ctx, int level, const float* img, int H, int W, const BlendPlan& pl, int K, const float* alpha, float* dst, int* ho, int* wo) {
   const float* wl = reinterpret_cast<const float*>(ctx->blendW.p) + pl.off[level];
-  if (int rc = encode_impl(ctx, ln, level, img, H, W, fC, nullptr, nullptr)) return rc;
-  if (int rc = moments_weighted_impl(ctx, ln, fC, C, h, w, wl, K, sum, sumsq)) return rc;
-  unsigned ident = 0;
-  double f[REG_MAX];
-  for (int k = 0; k < K; ++k) {
+  auto n_eff = [&](int k) -> double {
     const double v1 = pl.V1[level][k], v2 = pl.V2[level][k];
-    const bool active = v1 > 0. && v2 > 0. && v1 * v1 / v2 >= 2.;
-    f[k] = active ? v1 / v2 : 1.;
-    if (!active) ident |= 1u << k;
-  }
-  HIPCHK(ctx, launch_scale_sums(sum, sumsq, C, K, f, ln.stream));
-  for (int k = 0; k < K; ++k) {
-    if (ident >> k & 1u) continue;
-    const double v1 = pl.V1[level][k], v2 = pl.V2[level][k];
-    if (int rc = eig_impl(ctx, ln, C, v1 * v1 / v2, sum + (size_t)k * C, sumsq + k * cc, 1, ctx->eigCR[k], sv.info)) return rc;
-  }
-  HIPCHK(ctx, hipStreamWaitEvent(ln.stream, ctx->ev_style[level], 0));
-  for (int k = 0; k < K; ++k)
-    if (!(ident >> k & 1u))
-      if (int rc = assemble_impl(ctx, C, ctx->eigCR[k], ctx->eigR[k][level], alpha[k], M + k * cc, b + (size_t)k * C)) return rc;
-  HIPCHK(ctx, launch_mb_identity(M, b, C, K, ident, ln.stream));
-  if (int rc = apply_mixed_impl(ctx, fC, C, (long)h * w, wl, K, M, b, fO)) return rc;
-  return decode_impl(ctx, level, fO, h, w, nullptr, dst);
+    return v1 > 0. && v2 > 0. && v1 * v1 / v2 >= 2. ? v1 * v1 / v2 : 0.;
+  };
+  return multi_style_level(
+      ctx, "stylize_blend", level, img, H, W, pl, K, alpha, false, dst, ho, wo,
+      [&](const float* fC, int C, int h, int w, double*, double* sum, double* sumsq) -> int {
+        if (int rc = moments_weighted_impl(ctx, ctx->main, fC, C, h, w, wl, K, sum, sumsq)) return rc;
+        double f[REG_MAX];
+        for (int k = 0; k < K; ++k) f[k] = n_eff(k) > 0. ? pl.V1[level][k] / pl.V2[level][k] : 1.;
+        HIPCHK(ctx, launch_scale_sums(sum, sumsq, C, K, f, ctx->main.stream));
+        return WCT_OK;
+      },
+      n_eff, [&](const float* fC, int C, long npix, const double* M, const double* b, float* fO) { return apply_mixed_impl(ctx, fC, C, npix, wl, K, M, b, fO); });
 }
 }  // namespace
 
@@ -2916,14 +2879,7 @@ int wct_apply_mixed(wct_ctx* ctx, const float* feat, int C, int h, int w, int la
   const long npix = (long)h * w;
   if (layout == WCT_LAYOUT_NHWC) return apply_mixed_impl(ctx, feat, C, npix, weights, K, M, b, out);
   if (layout != WCT_LAYOUT_NCHW) return fail(ctx, WCT_ERR_INVALID, "apply_mixed: bad layout %d", layout);
-  const size_t fbytes = (size_t)npix * C * sizeof(float);
-  if (int rc = ensure(ctx, ctx->tmpT, 2 * fbytes)) return rc;
-  float* t0 = reinterpret_cast<float*>(ctx->tmpT.p);
-  float* t1 = t0 + (size_t)npix * C;
-  HIPCHK(ctx, launch_nchw_to_nhwc(feat, t0, C, (int)npix, ctx->main.stream));
-  if (int rc = apply_mixed_impl(ctx, t0, C, npix, weights, K, M, b, t1)) return rc;
-  HIPCHK(ctx, launch_nhwc_to_nchw(t1, out, C, (int)npix, ctx->main.stream));
-  return WCT_OK;
+  return apply_nchw(ctx, feat, C, npix, out, [&](const float* in, float* res) { return apply_mixed_impl(ctx, in, C, npix, weights, K, M, b, res); });
 }
 
 int wct_style_blend(wct_ctx* ctx, int level, int K, const double* stats, const float* lambda) {
@@ -2956,25 +2912,10 @@ int wct_stylize_interp(wct_ctx* ctx, const float* content, int H, int W, int K, 
   if (int rc = with_deferred_solves(ctx, false, [&]() -> int {
         if (int rc = fork_side(ctx)) return rc;
         if (int rc = interp_style_side(ctx, 5, K, styles, Hs, Ws, lam)) return rc;
-        // as cascade(): `out` doubles as the running image; the blended slot of level L - 1 is enqueued behind level L's content side
-        const size_t img_bytes = (size_t)3 * H * W * sizeof(float);
-        if (int rc = ensure(ctx, ctx->tmpT, img_bytes)) return rc;
-        float* bufs[2] = {reinterpret_cast<float*>(ctx->tmpT.p), out};
-        const float* cur = content;
-        int h = H, w = W, which = (5 * num_run) & 1;
-        for (int run = 0; run < num_run; ++run)
-          for (int level = 5; level >= 1; --level) {
-            int ho, wo;
-            float* dst = bufs[which];
-            if (int rc = content_side(ctx, level, cur, h, w, alpha, dst, &ho, &wo)) return rc;
-            if (run == 0 && level > 1)
-              if (int rc = interp_style_side(ctx, level - 1, K, styles, Hs, Ws, lam)) return rc;
-            cur = dst; h = ho; w = wo; which ^= 1;
-          }
-        if (cur != out) HIPCHK(ctx, hipMemcpyAsync(out, cur, (size_t)3 * h * w * sizeof(float), hipMemcpyDeviceToDevice, ctx->main.stream));
-        if (Ho) *Ho = h;
-        if (Wo) *Wo = w;
-        return WCT_OK;
+        return run_cascade(
+            ctx, content, H, W, num_run, out, Ho, Wo,
+            [&](int level, const float* cur, int h, int w, float* dst, int* ho, int* wo) { return content_side(ctx, level, cur, h, w, alpha, dst, ho, wo); },
+            [&](int level) { return interp_style_side(ctx, level - 1, K, styles, Hs, Ws, lam); });
       })) return rc;
   return range_readback(ctx);
 }
@@ -2991,13 +2932,7 @@ int wct_stylize_blend(wct_ctx* ctx, const float* content, int H, int W, const fl
   // the pooled weight maps of the five levels, their (V1, V2) and the weight check, read back ONCE: the solvers take each style's
   // n_eff on the host, and the weights are checked before anything is written to `out`
   BlendPlan pl{};
-  size_t total = 0;
-  for (int level = 5; level >= 1; --level) {
-    pl.h[level] = (H >> 4) << (5 - level);
-    pl.w[level] = (W >> 4) << (5 - level);
-    pl.off[level] = total;
-    total += ((size_t)K * pl.h[level] * pl.w[level] + 63) & ~(size_t)63;
-  }
+  const size_t total = level_geom(pl, H, W, K, 64);
   if (int rc = ensure(ctx, ctx->blendW, total * sizeof(float))) return rc;
   if (int rc = ensure(ctx, ctx->blendStat, BLEND_STAT_BYTES)) return rc;
   if (int rc = ensure(ctx, ctx->wsBlendPool, weights_levels_workspace_bytes(H, W))) return rc;
@@ -3024,27 +2959,11 @@ int wct_stylize_blend(wct_ctx* ctx, const float* content, int H, int W, const fl
     }
   if (int rc = with_deferred_solves(ctx, false, [&]() -> int {
         if (int rc = fork_side(ctx)) return rc;
-        for (int k = 0; k < K; ++k)
-          if (int rc = style_side_slot(ctx, 5, k, styles[k], Hs[k], Ws[k])) return rc;
-        const size_t img_bytes = (size_t)3 * H * W * sizeof(float);
-        if (int rc = ensure(ctx, ctx->tmpT, img_bytes)) return rc;
-        float* bufs[2] = {reinterpret_cast<float*>(ctx->tmpT.p), out};
-        const float* cur = content;
-        int h = H, w = W, which = (5 * num_run) & 1;
-        for (int run = 0; run < num_run; ++run)
-          for (int level = 5; level >= 1; --level) {
-            float* dst = bufs[which];
-            if (int rc = blend_level(ctx, level, cur, h, w, pl, K, alpha, dst)) return rc;
-            if (run == 0 && level > 1)
-              for (int k = 0; k < K; ++k)
-                if (int rc = style_side_slot(ctx, level - 1, k, styles[k], Hs[k], Ws[k])) return rc;
-            h = pl.h[level] << (level - 1); w = pl.w[level] << (level - 1);
-            cur = dst; which ^= 1;
-          }
-        if (cur != out) HIPCHK(ctx, hipMemcpyAsync(out, cur, (size_t)3 * h * w * sizeof(float), hipMemcpyDeviceToDevice, ctx->main.stream));
-        if (Ho) *Ho = h;
-        if (Wo) *Wo = w;
-        return WCT_OK;
+        if (int rc = style_side_slots(ctx, 5, K, styles, Hs, Ws)) return rc;
+        return run_cascade(
+            ctx, content, H, W, num_run, out, Ho, Wo,
+            [&](int level, const float* cur, int h, int w, float* dst, int* ho, int* wo) { return blend_level(ctx, level, cur, h, w, pl, K, alpha, dst, ho, wo); },
+            [&](int level) { return style_side_slots(ctx, level - 1, K, styles, Hs, Ws); });
       })) return rc;
   return range_readback(ctx);
 }
@@ -3216,33 +3135,24 @@ int wct_stylize_swap(wct_ctx* ctx, const float* content, int H, int W, const flo
   if (int rc = swap_level_dims(ctx, "wct_stylize_swap", swap_level, Hl, Wl, Hs, Ws, C, h, w, hs, ws)) return rc;
   // every buffer of the swap first (level 5 of a first run sees the un-cropped content; its feature map is the cropped one's)
   if (int rc = swap_bufs(ctx, C, h, w, hs, ws, match_mode == WCT_SWAP_WHITENED)) return rc;
-  if (int rc = ensure(ctx, ctx->tmpT, (size_t)3 * H * W * sizeof(float))) return rc;
-  float* bufs[2] = {reinterpret_cast<float*>(ctx->tmpT.p), out};
-  const float* cur = content;
-  int ch = H, cw = W, which = (5 * num_run) & 1;   // so that the last level writes into `out`
-  for (int run = 0; run < num_run; ++run)
-    for (int level = 5; level >= 1; --level) {
-      int ho = 0, wo = 0;
-      float* dst = bufs[which];
-      if (level == swap_level) {
-        int lc, lh, lw, lhs, lws;
-        if (int rc = swap_level_dims(ctx, "wct_stylize_swap", level, ch, cw, Hs, Ws, lc, lh, lw, lhs, lws)) return rc;
-        if (int rc = swap_level_impl(ctx, level, cur, ch, cw, style, Hs, Ws, lc, lh, lw, lhs, lws, match_mode, alpha, dst)) return rc;
-        ho = lh << (level - 1); wo = lw << (level - 1);
-      } else {
-        if (int rc = with_deferred_solves(ctx, false, [&]() -> int {
-              if (int rc = fork_side(ctx)) return rc;
-              if (int rc = style_side(ctx, level, style, Hs, Ws)) return rc;
-              return content_side(ctx, level, cur, ch, cw, alpha, dst, &ho, &wo);
-            })) return rc;
-      }
-      if (int rc = range_readback(ctx)) return rc;
-      cur = dst; ch = ho; cw = wo; which ^= 1;
-    }
-  if (cur != out) HIPCHK(ctx, hipMemcpyAsync(out, cur, (size_t)3 * ch * cw * sizeof(float), hipMemcpyDeviceToDevice, ctx->main.stream));
-  if (Ho) *Ho = ch;
-  if (Wo) *Wo = cw;
-  return WCT_OK;
+  return run_cascade(
+      ctx, content, H, W, num_run, out, Ho, Wo,
+      [&](int level, const float* cur, int ch, int cw, float* dst, int* ho, int* wo) -> int {
+        if (level == swap_level) {
+          int lc, lh, lw, lhs, lws;
+          if (int rc = swap_level_dims(ctx, "wct_stylize_swap", level, ch, cw, Hs, Ws, lc, lh, lw, lhs, lws)) return rc;
+          if (int rc = swap_level_impl(ctx, level, cur, ch, cw, style, Hs, Ws, lc, lh, lw, lhs, lws, match_mode, alpha, dst)) return rc;
+          *ho = lh << (level - 1); *wo = lw << (level - 1);
+        } else {
+          if (int rc = with_deferred_solves(ctx, false, [&]() -> int {
+                if (int rc = fork_side(ctx)) return rc;
+                if (int rc = style_side(ctx, level, style, Hs, Ws)) return rc;
+                return content_side(ctx, level, cur, ch, cw, alpha, dst, ho, wo);
+              })) return rc;
+        }
+        return range_readback(ctx);   // per level: the call ends without one of its own
+      },
+      [](int) { return (int)WCT_OK; });
 }
 
 }  // extern "C"

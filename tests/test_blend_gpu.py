@@ -265,6 +265,34 @@ def test_bad_weights_raise_before_writing_and_repeats_are_bitwise(torch_cuda, wc
         wct16.stylize_blend(c, styles * 5, cu(torch, np.zeros((10, H, W), np.float32)), 1.0)     # K = 10
 
 
+@pytest.mark.parametrize("H,W", [(64, 80), (70, 90)])
+def test_interp_and_blend_num_run_equal_chained_runs(torch_cuda, wct16, H, W):
+    """num_run = 2 and 3 of wct_stylize_interp / wct_stylize_blend against chained single-run calls, bit for bit: the two run counts
+    take both parities of the ping-pong between the caller's `out` and the context's buffer (`which = (5 * num_run) & 1`).  64 x 80
+    carries over unchanged; 70 x 90 is cropped to 64 x 80 by the first run, and the chained runs get the weight maps cropped top-left
+    to that size (the level maps are pooled from the top-left, so they are the same maps).  With a caller's `out` an even number
+    of levels must still end in that buffer."""
+    torch = torch_cuda
+    rng = np.random.default_rng(37)
+    Hc, Wc = H // 16 * 16, W // 16 * 16
+    c = cu(torch, _smooth(rng, (3, H, W)))
+    styles = [cu(torch, _smooth(rng, (3, 48, 64))), cu(torch, rng.random((3, 48, 64), dtype=np.float32))]
+    wts = cu(torch, _maps("gradient", H, W, rng))
+    calls = {"interp": lambda img, n, out=None: wct16.stylize_interp(img, styles, [0.3, 0.7], 0.8, num_run=n, out=out),
+             "blend": lambda img, n, out=None: wct16.stylize_blend(img, styles, wts[:, :img.shape[-2], :img.shape[-1]], [1.0, 0.7], num_run=n, out=out)}
+    for name, run in calls.items():
+        one = run(c, 1).clone()
+        assert tuple(one.shape) == (1, 3, Hc, Wc), name
+        two, three = run(c, 2).clone(), run(c, 3).clone()
+        chained2 = run(one, 1).clone()
+        chained3 = run(chained2, 1).clone()
+        assert torch.equal(two, chained2), name
+        assert torch.equal(three, chained3), name
+        out = torch.full((3, H, W), -3.0, device="cuda")
+        got = run(c, 2, out)
+        assert got.data_ptr() == out.data_ptr() and torch.equal(got, chained2), name
+
+
 def test_uhd_frame_gradient_vs_blend_oracle(torch_cuda, oracle, weights16x, wct16):
     torch = torch_cuda
     H, W = 2160, 3840

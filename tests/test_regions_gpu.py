@@ -226,6 +226,38 @@ def test_tiny_regions_bad_labels_and_repeatability(torch_cuda, wct16, oracle, we
         wct16.stylize_regions(cu(torch, c), cs * 3, lab_d, 1.0)            # K = 9
 
 
+@pytest.mark.parametrize("H,W", [(64, 80), (70, 90)])
+def test_regions_num_run_equals_chained_runs(torch_cuda, wct16, H, W):
+    """num_run = 2 and 3 of wct_stylize_regions against chained single-run calls, bit for bit: the two run counts take both parities
+    of the ping-pong between the caller's `out` and the context's buffer (`which = (5 * num_run) & 1`).  64 x 80 carries over
+    unchanged; 70 x 90 is cropped to 64 x 80 by the first run, and the chained runs get the label map cropped top-left to that size
+    (the level maps are sampled from the top-left, so they are the same maps).  With a caller's `out` an even number of levels must
+    still end in that buffer."""
+    torch = torch_cuda
+    rng = np.random.default_rng(17)
+    Hc, Wc = H // 16 * 16, W // 16 * 16
+    c = cu(torch, _smooth(rng, (3, H, W)))
+    styles = [cu(torch, _smooth(rng, (3, 48, 64))), cu(torch, rng.random((3, 48, 64), dtype=np.float32))]
+    lab = np.zeros((H, W), np.uint8)
+    lab[:, W // 2:] = 1
+    lab[:8] = 255
+    lab = cu(torch, lab)
+
+    def run(img, n, out=None):
+        return wct16.stylize_regions(img, styles, lab[:img.shape[-2], :img.shape[-1]], [1.0, 0.7], num_run=n, out=out)
+
+    one = run(c, 1).clone()
+    assert tuple(one.shape) == (1, 3, Hc, Wc)
+    two, three = run(c, 2).clone(), run(c, 3).clone()
+    chained2 = run(one, 1).clone()
+    chained3 = run(chained2, 1).clone()
+    assert torch.equal(two, chained2)
+    assert torch.equal(three, chained3)
+    out = torch.full((3, H, W), -3.0, device="cuda")
+    got = run(c, 2, out)
+    assert got.data_ptr() == out.data_ptr() and torch.equal(got, chained2)
+
+
 # ---------------------------------------------------------------------------------------------------- 7. a 4K frame
 def test_uhd_frame_two_regions(torch_cuda, wct16):
     torch = torch_cuda
