@@ -251,6 +251,7 @@ hipError_t launch_patch_match(const float* q, int h, int w, const float* k, int 
   const int qtiles_x = (qw + SW_TX - 1) / SW_TX, qtiles_y = (qh + SW_TY - 1) / SW_TY;
   const int ktiles_x = (kw + SW_TX - 1) / SW_TX;
   const long qtiles = (long)qtiles_x * qtiles_y;
+  int nlaunch = 0, nkt_first = 0, split_first = 0, nkt_last = 0, split_last = 0;
   for (long c0 = 0; c0 < nk; c0 += key_chunk) {
     const long c1 = c0 + key_chunk < nk ? c0 + key_chunk : nk;
     const int ky0 = (int)(c0 / kw), ky1 = (int)((c1 - 1) / kw);          // the band of key rows the chunk touches
@@ -261,7 +262,13 @@ hipError_t launch_patch_match(const float* q, int h, int w, const float* k, int 
     if (split > 65535) split = 65535;
     hipLaunchKernelGGL(swap_match_kernel, dim3((unsigned)qtiles, (unsigned)split), dim3(SW_THREADS), 0, s, q, h, w, k, hs, ws, C, rnorm, (int)c0,
                        (int)c1, ky0, ktiles_x, nkt, qtiles_x, r, sat);
+    if (!nlaunch++) { nkt_first = nkt; split_first = (int)split; }
+    nkt_last = nkt; split_last = (int)split;
   }
+  // "prof_forms": q<query tiles>.l<launches>.<key tiles>/<grid.y> of the first launch.<the same of the last> (include/wct_hip.h)
+  char form[sizeof wct_launch_form.text];
+  snprintf(form, sizeof form, "q%ld.l%d.%d/%d.%d/%d", qtiles, nlaunch, nkt_first, split_first, nkt_last, split_last);
+  note_launch_text(form);
   hipLaunchKernelGGL(swap_final_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, s, r, nq, idx, best);
   return hipGetLastError();
 }

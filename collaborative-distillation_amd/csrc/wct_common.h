@@ -26,7 +26,7 @@ static inline const char* wct_debug_env(const char* name) {
 // form, '3' three-stage persistent kernel; 0 = the launcher has a single form and says nothing.  multi: the grid is smaller than
 // tiles x cout groups, so some workgroup walks more than one unit.
 // The plan-driven launchers of the feature-space kernels (launch_moments, launch_moments_labeled, launch_moments_weighted, the fold
-// launchers) leave a ready-made suffix in `text` instead (note_launch_text; grammar: include/wct_hip.h, "prof_forms"); ProfScope
+// launchers, launch_patch_match) leave a ready-made suffix in `text` instead (note_launch_text; grammar: include/wct_hip.h, "prof_forms"); ProfScope
 // appends ":<text>" (tests/test_sweep_gpu.py holds it against tests/sweep_cases.py).  Defined in wct_api.hip; not part of the ABI.
 struct LaunchForm { char form; int tile_h; bool multi; char text[24]; };
 extern __thread LaunchForm wct_launch_form __attribute__((visibility("hidden")));

@@ -133,6 +133,11 @@ int wct_range_flag_f64(wct_ctx* ctx, double* flag_dev);
  *   "fold_affine"  ":fra" / ":frg" = fold_row_kernel's aligned / generic path, ":fb" = fold_block_kernel (cin >= 256), ":fg" = the fp64
  *                  GEMM fold, ":ff" = the fast fold
  * (tests/sweep_cases.py restates the plans, tests/test_sweep_gpu.py holds every report against it).
+ *   "patch_match<f16x3>"  ":q<QT>.l<L>.<nkt>/<split>.<nkt>/<split>" -- QT = query tiles (grid.x of every match launch), L = match launches
+ *                  (key chunks), then the key tiles of the band and the workgroups per query tile they are dealt to (grid.y) of the
+ *                  FIRST launch and of the LAST one (the same pair twice when L = 1); a workgroup walks ceil(nkt / split) key tiles at
+ *                  the most -- e.g. "patch_match<f16x3>:q16.l2.68/64.34/34".  Cut at 23 characters
+ *                  (tests/swap_cases.py restates the launcher, tests/test_swap_edges_gpu.py holds every report against it).
  * "poison" (a byte 0..255, or -1 = off) is the test hook for "does a call read what an earlier call left in the workspace": it
  * synchronises both of the context's streams, fills every allocated SCRATCH buffer of the context with that byte and, until it is
  * turned off, every buffer the workspace allocates later as well (a grown buffer is a fresh allocation and usually zero pages).
