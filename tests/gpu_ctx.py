@@ -1,5 +1,5 @@
 """One wct_ctx driven through the C ABI with numpy in and numpy out: the harness of the GPU tests that load modules of their own
-(tests/test_widths_gpu.py, tests/test_range_gpu.py, tests/test_sweep_gpu.py).  The WCT class hard-codes model_zoo's widths; `wct_load_module` takes any layer list."""
+(tests/test_widths_gpu.py, tests/test_range_gpu.py, tests/test_sweep_gpu.py, tests/test_conv_sweep_gpu.py).  The WCT class hard-codes model_zoo's widths; `wct_load_module` takes any layer list."""
 import ctypes
 from ctypes import byref, c_int, c_void_p
 
@@ -86,13 +86,17 @@ class Ctx:
         self.chk(self.L.wct_profile_enable(self.ctx, 1))
         self.chk(self.L.wct_profile_reset(self.ctx))
 
-    def profile_names(self):
+    def profile_counts(self):
+        """{profile name: launches} since profile_start(); turns profiling off"""
         n = c_int()
         self.chk(self.L.wct_profile_read(self.ctx, None, 0, byref(n)))
         e = (_lib.WctProfEntry * max(n.value, 1))()
         self.chk(self.L.wct_profile_read(self.ctx, e, n.value, byref(n)))
         self.chk(self.L.wct_profile_enable(self.ctx, 0))
-        return {e[i].name.decode() for i in range(n.value)}
+        return {e[i].name.decode(): int(e[i].launches) for i in range(n.value)}
+
+    def profile_names(self):
+        return set(self.profile_counts())
 
     # ---- entry points
     def encode(self, level, img):
