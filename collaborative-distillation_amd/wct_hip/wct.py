@@ -142,11 +142,19 @@ class WCT:
                                 "(trained_models/original_wct_models/*.t7, not in the reference snapshot; read by wct_hip/t7.py) "
                                 "-- or pass weights=...")
 
+    def _layers(self, kind: str, level: int):
+        """The layer list of one module ("enc" | "dec") of a level: the shipped graphs by mode.  The one place the class reads
+        model_zoo's layer tables (a subclass with widths of its own overrides this and _feature_channels)."""
+        return model_zoo.encoder_layers(self.mode, level) if kind == "enc" else model_zoo.decoder_layers(self.mode, level)
+
+    def _feature_channels(self, level: int) -> int:
+        """Channels of the level's feature map (relu{level}_1)."""
+        return model_zoo.feature_channels(self.mode, level)
+
     def _load_modules(self, w: Dict[str, np.ndarray]):
         self._keep = []  # host arrays must outlive wct_load_module only, but keep them for clarity
         for k in range(1, 6):
-            for kind, kid, layers in (("enc", _lib.KIND_ENC, model_zoo.encoder_layers(self.mode, k)),
-                                      ("dec", _lib.KIND_DEC, model_zoo.decoder_layers(self.mode, k))):
+            for kind, kid, layers in (("enc", _lib.KIND_ENC, self._layers("enc", k)), ("dec", _lib.KIND_DEC, self._layers("dec", k))):
                 key = model_zoo.module_key(kind, k)
                 arr = (_lib.WctLayer * len(layers))()
                 hold = []
@@ -275,7 +283,7 @@ class WCT:
             raise ValueError("expected a [1,C,h,w] / [C,h,w] (nchw) or [1,h,w,C] / [h,w,C] (nhwc) feature, got %s" % (tuple(feat.shape),))
         f = self._dev_f32(f)
         nchw = layout == "nchw"
-        C = model_zoo.feature_channels(self.mode, level)
+        C = self._feature_channels(level)
         if nchw:
             c, h, w = (int(s) for s in f.shape)
         else:
@@ -374,7 +382,7 @@ class WCT:
 
     @torch.no_grad()
     def decode_affine(self, level: int, feat_nhwc: torch.Tensor, M: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
-        C = model_zoo.feature_channels(self.mode, level)
+        C = self._feature_channels(level)
         f = self._nhwc(feat_nhwc, C)
         M, b = self._dev_f64(M, C * C, "M"), self._dev_f64(b, C, "b")
         h, w, _ = (int(v) for v in f.shape)
@@ -512,7 +520,7 @@ class WCT:
         x = self._img(img)
         self._content_keep = x
         H, W = int(x.shape[1]), int(x.shape[2])
-        C = model_zoo.feature_channels(self.mode, level)
+        C = self._feature_channels(level)
         s = torch.empty(C, device=x.device, dtype=torch.float64)
         ss = torch.empty(C, C, device=x.device, dtype=torch.float64)
         h, w = c_int(), c_int()
@@ -523,7 +531,7 @@ class WCT:
     @torch.no_grad()
     def content_solve(self, level: int, n_c: float, sum_c: torch.Tensor, sumsq_c: torch.Tensor, alpha: Optional[float] = None):
         alpha = self.alpha if alpha is None else float(alpha)
-        C = model_zoo.feature_channels(self.mode, level)
+        C = self._feature_channels(level)
         sum_c, sumsq_c = self._dev_f64(sum_c, C, "sum_c"), self._dev_f64(sumsq_c, C * C, "sumsq_c")
         M = torch.empty(C, C, device=sum_c.device, dtype=torch.float64)
         b = torch.empty(C, device=sum_c.device, dtype=torch.float64)
@@ -637,7 +645,7 @@ class WCT:
         context's side stream, visible to the caller's stream (wct_style_moments; the style side of sharded.py's "strips" mode)."""
         x = self._img(style_strip)
         self._style_keep = x
-        C = model_zoo.feature_channels(self.mode, level)
+        C = self._feature_channels(level)
         s = torch.empty(C, device=x.device, dtype=torch.float64)
         ss = torch.empty(C, C, device=x.device, dtype=torch.float64)
         self._stream()
@@ -647,7 +655,7 @@ class WCT:
     @torch.no_grad()
     def style_solve(self, level: int, n_s: float, sum_s: torch.Tensor, sumsq_s: torch.Tensor) -> None:
         """Global style moments of a level -> cov_s^(1/2), mu_s inside the context (what style_prepare leaves), on the side stream."""
-        C = model_zoo.feature_channels(self.mode, level)
+        C = self._feature_channels(level)
         sum_s, sumsq_s = self._dev_f64(sum_s, C, "sum_s"), self._dev_f64(sumsq_s, C * C, "sumsq_s")
         self._solve_keep = getattr(self, "_solve_keep", {})
         self._solve_keep[level] = (sum_s, sumsq_s)       # read asynchronously by the side stream
