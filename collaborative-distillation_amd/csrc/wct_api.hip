@@ -3,6 +3,7 @@
 // in the kernels of conv3x3.hip / moments.hip / solve.hip / misc.hip.
 #include "../../include/wct_hip.h"
 #include "../../include/wct_hip_color.h"
+#include "../../include/wct_hip_scale.h"
 #include "../../include/wct_hip_smooth.h"
 #include "../../include/wct_hip_swap.h"
 #include "../../include/wct_hip_transform.h"
@@ -115,6 +116,9 @@ struct wct_ctx {
   // (score, index) of every query between the key chunks' launches, the key norms, and the all-zero label map of the one-label affine apply
   DevBuf swFc, swFs, swQ, swK, swOut, swIdx, swRun, swNorm, swLab;
   int swap_key_chunk = 0;   // debug key "swap_key_chunk": keys per launch of the match; 0 = WCT_SWAP_KEY_CHUNK
+  // scale control (include/wct_hip_scale.h): the content at the working size of every distinct divisor of wct_stylize_scaled, and the
+  // image its merges and levels ping-pong through with the caller's `out`
+  DevBuf scF[5], scStage, scTab;   // scTab: the weight tables of one resampler / merge launch (scale.hip)
   DevBuf l1img;       // level 1 fused: copy of the content image between wct_content_encode and wct_content_decode
   int cur_H = 0, cur_W = 0;
   int numpy_variant = 0;  // 1: `--numpy` semantics (util_wct.py:143): + I on the CONTENT covariance
@@ -191,6 +195,9 @@ struct wct_ctx {
                       &regLab, &regHist, &regSums, &regMb, &regFeat, &wsRegMom, &wsRegApply,
                       &blendW, &blendStat, &wsBlendPool, &wsBlendApply})
       f(*b, &main, true);
+    for (DevBuf& b : scF) f(b, &main, true);
+    f(scStage, &main, true);
+    f(scTab, &main, true);
     for (DevBuf& b : eigCR) f(b, &main, true);       // the regions' content-side results: rewritten by every level that reads them
     for (DevBuf* b : {&featC, &l1img}) f(*b, &main, !pair_open);
     for (int l = 0; l < 6; ++l) {
@@ -3153,6 +3160,179 @@ int wct_stylize_swap(wct_ctx* ctx, const float* content, int H, int W, const flo
         return range_readback(ctx);   // per level: the call ends without one of its own
       },
       [](int) { return (int)WCT_OK; });
+}
+
+}  // extern "C"
+
+// ---- scale control (include/wct_hip_scale.h; kernel in scale.hip) --------------------------------------------------------------------
+namespace {
+// the shapes both image calls accept; `who` names the entry
+int scale_shapes_check(wct_ctx* ctx, const char* who, int H, int W, int oH, int oW) {
+  if (H < 1 || W < 1 || oH < 1 || oW < 1) return fail(ctx, WCT_ERR_INVALID, "%s: empty shape (%dx%d -> %dx%d)", who, H, W, oH, oW);
+  if ((long)H > (long)WCT_SCALE_MAX_SHRINK * oH || (long)W > (long)WCT_SCALE_MAX_SHRINK * oW)
+    return fail(ctx, WCT_ERR_INVALID, "%s: %dx%d -> %dx%d shrinks an axis by more than %d", who, H, W, oH, oW, WCT_SCALE_MAX_SHRINK);
+  return WCT_OK;
+}
+
+// algorithmic products of R: every output sample of a pass takes its taps once
+double resample_flops(int H, int W, int oH, int oW, int filter) {
+  const double S = filter == WCT_FILTER_BICUBIC ? 2.0 : 1.0;
+  const double tx = 2.0 * S * std::max((double)W / oW, 1.0), ty = 2.0 * S * std::max((double)H / oH, 1.0);
+  return 2.0 * 3.0 * ((double)H * oW * tx + (double)oH * oW * ty);
+}
+
+int resample_impl(wct_ctx* ctx, const float* src, int H, int W, float* dst, int oH, int oW, int filter) {
+  if (H == oH && W == oW) {   // equal sizes: a bit-for-bit copy
+    ProfScope ps(ctx, ctx->main.stream, "resample<copy>", 0, 24.0 * H * W);
+    HIPCHK(ctx, hipMemcpyAsync(dst, src, (size_t)3 * H * W * sizeof(float), hipMemcpyDeviceToDevice, ctx->main.stream));
+    return WCT_OK;
+  }
+  if (int rc = ensure(ctx, ctx->scTab, scale_table_bytes(H, W, oH, oW, filter))) return rc;
+  char name[48];
+  snprintf(name, sizeof name, "resample<%s,%s>", filter == WCT_FILTER_BICUBIC ? "bicubic" : "bilinear", (double)oH * oW < (double)H * W ? "down" : "up");
+  ProfScope ps(ctx, ctx->main.stream, name, resample_flops(H, W, oH, oW, filter), 12.0 * ((double)H * W + (double)oH * oW));
+  HIPCHK(ctx, launch_scale(src, nullptr, nullptr, 0.f, H, W, dst, oH, oW, filter, ctx->scTab.p, ctx->scTab.cap, ctx->main.stream));
+  return WCT_OK;
+}
+
+int merge_impl(wct_ctx* ctx, const float* a, const float* b, int hc, int wc, const float* c, int hf, int wf, float gain, float* out) {
+  if (gain == 0.f) return resample_impl(ctx, a, hc, wc, out, hf, wf, WCT_FILTER_BICUBIC);   // exactly R(a): b and c are not read
+  if (int rc = ensure(ctx, ctx->scTab, scale_table_bytes(hc, wc, hf, wf, WCT_FILTER_BICUBIC))) return rc;
+  ProfScope ps(ctx, ctx->main.stream, "pyramid_merge", resample_flops(hc, wc, hf, wf, WCT_FILTER_BICUBIC) + 12.0 * ((double)hc * wc + (double)hf * wf),
+               12.0 * (2.0 * hc * wc + 2.0 * hf * wf));
+  HIPCHK(ctx, launch_scale(a, b, c, gain, hc, wc, out, hf, wf, WCT_FILTER_BICUBIC, ctx->scTab.p, ctx->scTab.cap, ctx->main.stream));
+  return WCT_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int wct_scale_shape(int H, int W, int divisor, int* h, int* w) {
+  if (!h || !w || H < 1 || W < 1 || divisor < 1 || divisor > WCT_SCALE_MAX_DIVISOR) return WCT_ERR_INVALID;
+  const int hd = 16 * (H / (16 * divisor)), wd = 16 * (W / (16 * divisor));
+  if (hd < 32 || wd < 32) return WCT_ERR_INVALID;
+  *h = hd; *w = wd;
+  return WCT_OK;
+}
+
+int wct_resample_planar(wct_ctx* ctx, const float* src, int H, int W, float* dst, int oH, int oW, int filter) {
+  if (!ctx) return WCT_ERR_INVALID;
+  WCT_GUARD(ctx);
+  if (!src || !dst) return fail(ctx, WCT_ERR_INVALID, "wct_resample_planar: NULL image");
+  if (int rc = scale_shapes_check(ctx, "wct_resample_planar", H, W, oH, oW)) return rc;
+  if (filter != WCT_FILTER_BILINEAR && filter != WCT_FILTER_BICUBIC)
+    return fail(ctx, WCT_ERR_INVALID, "wct_resample_planar: filter %d is neither WCT_FILTER_BILINEAR (0) nor WCT_FILTER_BICUBIC (1)", filter);
+  if (ranges_overlap(dst, (size_t)3 * oH * oW * sizeof(float), src, (size_t)3 * H * W * sizeof(float)))
+    return fail(ctx, WCT_ERR_INVALID, "wct_resample_planar: dst overlaps src, which is read while it is written");
+  return resample_impl(ctx, src, H, W, dst, oH, oW, filter);
+}
+
+int wct_pyramid_merge(wct_ctx* ctx, const float* a, const float* b, int hc, int wc, const float* c, int hf, int wf, float gain, float* out) {
+  if (!ctx) return WCT_ERR_INVALID;
+  WCT_GUARD(ctx);
+  if (!a || !out) return fail(ctx, WCT_ERR_INVALID, "wct_pyramid_merge: NULL a or out");
+  if (!std::isfinite(gain) || gain < 0.f) return fail(ctx, WCT_ERR_INVALID, "wct_pyramid_merge: gain must be finite and >= 0, got %g", (double)gain);
+  if (gain > 0.f && (!b || !c)) return fail(ctx, WCT_ERR_INVALID, "wct_pyramid_merge: b and c may be NULL only when gain == 0 (got %g)", (double)gain);
+  if (int rc = scale_shapes_check(ctx, "wct_pyramid_merge", hc, wc, hf, wf)) return rc;
+  const size_t cb = (size_t)3 * hc * wc * sizeof(float), fb = (size_t)3 * hf * wf * sizeof(float);
+  if (ranges_overlap(out, fb, a, cb) || (gain > 0.f && (ranges_overlap(out, fb, b, cb) || ranges_overlap(out, fb, c, fb))))
+    return fail(ctx, WCT_ERR_INVALID, "wct_pyramid_merge: out overlaps a, b or c, which are read while it is written");
+  return merge_impl(ctx, a, b, hc, wc, c, hf, wf, gain, out);
+}
+
+int wct_stylize_scaled(wct_ctx* ctx, const float* content, int H, int W, const float* style, int Hs, int Ws, float alpha, int num_run,
+                       const int* level_div, float detail_gain, float* out, int* Ho, int* Wo) {
+  if (!ctx) return WCT_ERR_INVALID;
+  WCT_GUARD(ctx);
+  if (!content || !out || !level_div || num_run < 1)
+    return fail(ctx, WCT_ERR_INVALID, "wct_stylize_scaled: bad arguments (a NULL content, out or level_div, or num_run < 1)");
+  if (!std::isfinite(detail_gain) || detail_gain < 0.f)
+    return fail(ctx, WCT_ERR_INVALID, "wct_stylize_scaled: detail_gain must be finite and >= 0, got %g", (double)detail_gain);
+  if (H < 1 || W < 1 || (style && (Hs < 1 || Ws < 1)))
+    return fail(ctx, WCT_ERR_INVALID, "wct_stylize_scaled: bad shapes (content %dx%d, style %dx%d)", H, W, Hs, Ws);
+  int hd[5], wd[5];   // working size of levels 5, 4, 3, 2, 1
+  for (int i = 0; i < 5; ++i) {
+    const int d = level_div[i];
+    if (d < 1 || d > WCT_SCALE_MAX_DIVISOR)
+      return fail(ctx, WCT_ERR_INVALID, "wct_stylize_scaled: divisor %d of level %d is outside 1 .. %d", d, 5 - i, WCT_SCALE_MAX_DIVISOR);
+    if (i > 0 && d > level_div[i - 1])
+      return fail(ctx, WCT_ERR_INVALID, "wct_stylize_scaled: divisors must not increase towards level 1 (level %d has %d, level %d has %d)", 6 - i,
+                  level_div[i - 1], 5 - i, d);
+    if (wct_scale_shape(H, W, d, &hd[i], &wd[i]))
+      return fail(ctx, WCT_ERR_INVALID, "wct_stylize_scaled: content %dx%d at divisor %d is under the 32x32 the five-level cascade needs", H, W, d);
+  }
+  if (level_div[4] != 1) return fail(ctx, WCT_ERR_INVALID, "wct_stylize_scaled: the divisor of level 1 must be 1, got %d", level_div[4]);
+  if (ranges_overlap(out, (size_t)3 * hd[4] * wd[4] * sizeof(float), content, (size_t)3 * H * W * sizeof(float)))
+    return fail(ctx, WCT_ERR_INVALID, "wct_stylize_scaled: out overlaps the content, which the merges still read");
+  if (!style)
+    for (int level = 5; level >= 1; --level)
+      if (!ctx->eigS[level].p)
+        return fail(ctx, WCT_ERR_STATE, "wct_stylize_scaled: no style statistics for level %d (wct_style_prepare / wct_style_import)", level);
+  if (level_div[0] == 1)   // every divisor is 1: the plain cascade, bit for bit
+    return style ? stylize_impl(ctx, content, H, W, style, Hs, Ws, alpha, num_run, out, Ho, Wo)
+                 : stylize_prepared_impl(ctx, "wct_stylize_scaled", content, H, W, alpha, num_run, out, Ho, Wo);
+
+  // every buffer first: a growing one synchronises, and nothing enqueued below may find its source moved
+  const float* F[5];   // F_d of every level's divisor; equal divisors share one
+  for (int i = 0, slot = 0; i < 5; ++i) {
+    if (i > 0 && level_div[i] == level_div[i - 1]) { F[i] = F[i - 1]; continue; }
+    if (level_div[i] == 1 && hd[i] == H && wd[i] == W) { F[i] = content; continue; }
+    if (int rc = ensure(ctx, ctx->scF[slot], (size_t)3 * hd[i] * wd[i] * sizeof(float))) return rc;
+    F[i] = reinterpret_cast<const float*>(ctx->scF[slot++].p);
+  }
+  if (int rc = ensure(ctx, ctx->scStage, (size_t)3 * hd[4] * wd[4] * sizeof(float))) return rc;
+  {
+    size_t tab = scale_table_bytes(hd[4], wd[4], hd[0], wd[0], WCT_FILTER_BICUBIC);   // the reduction in front of a later run
+    for (int i = 0; i < 5; ++i) {
+      tab = std::max(tab, scale_table_bytes(H, W, hd[i], wd[i], WCT_FILTER_BICUBIC));                                // F_d
+      if (i > 0) tab = std::max(tab, scale_table_bytes(hd[i - 1], wd[i - 1], hd[i], wd[i], WCT_FILTER_BICUBIC));     // the merges
+    }
+    if (int rc = ensure(ctx, ctx->scTab, tab)) return rc;
+  }
+  for (int i = 0; i < 5; ++i)
+    if (F[i] != content && (i == 0 || F[i] != F[i - 1]))
+      if (int rc = resample_impl(ctx, content, H, W, const_cast<float*>(F[i]), hd[i], wd[i], WCT_FILTER_BICUBIC)) return rc;
+
+  int transitions = 0;
+  for (int i = 1; i < 5; ++i) transitions += level_div[i] != level_div[i - 1];
+  const int n_ops = num_run * (5 + transitions) + (num_run - 1);   // levels and merges of every run, and the reduction in front of every later run
+  float* bufs[2] = {out, reinterpret_cast<float*>(ctx->scStage.p)};
+  const bool interleaved = style && ctx->interleave && ctx->overlap;
+  if (int rc = with_deferred_solves(ctx, false, [&]() -> int {
+        if (style) {   // the style side as in wct_stylize: on the side lane, level L - 1 behind the content side of level L of the first run
+          if (int rc = fork_side(ctx)) return rc;
+          for (int level = 5; level >= (interleaved ? 5 : 1); --level)
+            if (int rc = style_side(ctx, level, style, Hs, Ws)) return rc;
+        }
+        int op = 0;   // operation `op` of n_ops writes bufs[(n_ops - 1 - op) & 1]: each reads what the one before wrote, the last writes `out`
+        const float* cur = F[0];
+        int h = hd[0], w = wd[0];
+        for (int run = 0; run < num_run; ++run) {
+          if (run > 0) {
+            float* dst = bufs[(n_ops - 1 - op++) & 1];
+            if (int rc = resample_impl(ctx, cur, h, w, dst, hd[0], wd[0], WCT_FILTER_BICUBIC)) return rc;
+            cur = dst; h = hd[0]; w = wd[0];
+          }
+          for (int i = 0; i < 5; ++i) {
+            const int level = 5 - i;
+            if (i > 0 && level_div[i] != level_div[i - 1]) {
+              float* dst = bufs[(n_ops - 1 - op++) & 1];
+              if (int rc = merge_impl(ctx, cur, F[i - 1], h, w, F[i], hd[i], wd[i], detail_gain, dst)) return rc;
+              cur = dst; h = hd[i]; w = wd[i];
+            }
+            float* dst = bufs[(n_ops - 1 - op++) & 1];
+            int ho = 0, wo = 0;
+            if (int rc = content_side(ctx, level, cur, h, w, alpha, dst, &ho, &wo)) return rc;
+            cur = dst; h = ho; w = wo;
+            if (interleaved && run == 0 && level > 1)
+              if (int rc = style_side(ctx, level - 1, style, Hs, Ws)) return rc;
+          }
+        }
+        return WCT_OK;
+      })) return rc;
+  if (Ho) *Ho = hd[4];
+  if (Wo) *Wo = wd[4];
+  return range_readback(ctx);
 }
 
 }  // extern "C"

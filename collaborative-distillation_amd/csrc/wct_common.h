@@ -181,6 +181,14 @@ void resize_axis_tables(int in_size, int out_size, int filter, int& ksize, std::
 hipError_t launch_resize_u8(const uint8_t* in, int H, int W, int oH, int oW, const int* bounds_h, const int* kk_h, int ksize_h,
                             const int* bounds_v_shifted, const int* kk_v, int ksize_v, int row0, int rows, uint8_t* tmp, uint8_t* out,
                             float* planar, hipStream_t s);
+// ---- scale control (scale.hip; include/wct_hip_scale.h): out = R(a -> oH x oW, filter) on planar 3 x H x W fp32, or with b (3 x H x W) and c
+// (3 x oH x oW) both given the merge R(a - gain b) + gain c; two launches (the weight tables into `tab`, the caller's scratch of
+// scale_table_bytes; then the tiles).  scale_tile_w / _h: the kernel's output tile at mild ratios.
+int scale_tile_w();
+int scale_tile_h();
+size_t scale_table_bytes(int H, int W, int oH, int oW, int filter);
+hipError_t launch_scale(const float* a, const float* b, const float* c, float gain, int H, int W, float* out, int oH, int oW, int filter, void* tab,
+                        size_t tab_bytes, hipStream_t s);
 
 // ---- pitched block copy of floats (rows x width; the sharded cascade's level crops, halo packing and assembly: a planar 3 x H x W image is
 //      3H rows of pitch W)

@@ -37,6 +37,10 @@ every 3x3 patch of the content feature is replaced by its best-matching style fe
 features (--swap_match whitened, the default) or on the features themselves (raw); the other levels keep --transform.  One pair at a time
 (wct_stylize_swap, the serial loop: the swapped level needs the style's feature map, not its statistics); --preserve_color luma and
 --smooth_radius follow as usual.  The files carry _swap=<L> in their names, after the transform mark.
+--level_scale d5,d4,d3,d2,d1 (not in the reference; Gatys et al. 2017, section 6: scale control) runs level L on the content reduced by the
+divisor dL and, where the working size grows, brings the running image up and puts the content's fine detail back (--scale_detail, a look);
+--coarse_style gives the reduced levels a style of their own (scale mixing).  One pair at a time (wct_stylize_scaled, the serial loop);
+--transform, --preserve_color and --smooth_radius go with it through the public calls around it.  The files carry _scale=<d5-d4-d3-d2-d1>.
 Decoding/encoding files needs Pillow on the host (the reference's own dependency); the GPU library is mandatory: there
 is no CPU fallback.
 """
@@ -118,6 +122,17 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--swap_match", type=str, default=None, choices=["whitened", "raw"],
                    help="where --swap_level matches patches: whitened = in the whitened domains of both features (Avatar-Net's style "
                         "decorator, the default), raw = on the features themselves (Chen & Schmidt)")
+    # not in the reference: scale control, a coarse-to-fine cascade on a device image pyramid (include/wct_hip_scale.h)
+    p.add_argument("--level_scale", type=str, default=None,
+                   help="d5,d4,d3,d2,d1: run level L of the cascade on the content reduced by the integer divisor dL (1 .. 16, not "
+                        "increasing towards level 1, d1 = 1), e.g. 4,4,2,1,1: the reduced levels lay down strokes dL times as large "
+                        "(default: off)")
+    p.add_argument("--scale_detail", type=float, default=None,
+                   help="with --level_scale: how much of the content's fine detail is put back where the working size grows (default "
+                        "1.0 = the Laplacian-pyramid step, 0 = plain upsampling); a look, not a measurement")
+    p.add_argument("--coarse_style", type=str, default=None,
+                   help="with --level_scale: a second style image for the levels whose divisor is > 1 (scale mixing); the other levels "
+                        "take the pair's style")
     return p
 
 
@@ -161,6 +176,9 @@ def out_name(args, imname: str) -> str:
     swap = getattr(args, "swap_level", None)
     if swap:
         tmark += "_swap=%d" % swap                                                              # after the transform mark
+    scale = getattr(args, "level_scale", None)
+    if scale:
+        tmark += "_scale=%s" % "-".join(t.strip() for t in scale.split(","))                    # in the same place (the two do not mix)
     marks = ("_color=%s" % color if color else "") + ("_smooth=%d" % radius if radius else "")   # runs with and without the flags never collide
     return os.path.join(args.outf, "%s_mode=%s_alpha=%s%s%s_%s" % (args.log_mark, args.mode, args.alpha, tmark, marks, imname))
 
@@ -378,6 +396,115 @@ def run_swap(args, wct, pairs, content_dir, style_dir, logprinter) -> float:
         t0 = time.time()
         c_f32 = _to_tensor(wct, c_u8, args.content_size)
         res = _swap_pair(wct, args, logprinter, c_f32, lambda: _to_tensor(wct, s_u8, args.style_size))
+        out = _finish_u8(wct, args, res, c_f32).cpu().numpy()   # .cpu() syncs
+        Image.fromarray(out).save(out_name(args, imname))
+        dt = time.time() - t0
+        avg += dt
+        logprinter("Elapsed time is: %.4f seconds" % dt)
+    return avg
+
+
+def level_scale_list(text: str) -> Tuple[int, ...]:
+    """'4,4,2,1,1' -> (4, 4, 2, 1, 1): the divisors of levels 5, 4, 3, 2, 1."""
+    try:
+        div = tuple(int(t) for t in text.split(","))
+    except ValueError:
+        raise ValueError("--level_scale: five comma-separated integers expected (d5,d4,d3,d2,d1), got %r" % (text,))
+    if len(div) != 5:
+        raise ValueError("--level_scale: five divisors expected (d5,d4,d3,d2,d1), got %d in %r" % (len(div), text))
+    return div
+
+
+def check_scale_args(args) -> None:
+    """--level_scale / --scale_detail / --coarse_style: one style per content (two with --coarse_style), a content to reduce, and the
+    affine cascade at every level; --transform, --numpy, --preserve_color and --smooth_radius go with it.  Fills in the default gain."""
+    from .lib import SCALE_DETAIL, SCALE_MAX_DIVISOR
+    text, gain, coarse = getattr(args, "level_scale", None), getattr(args, "scale_detail", None), getattr(args, "coarse_style", None)
+    if not text:
+        for flag, name in ((gain is not None, "--scale_detail"), (coarse is not None, "--coarse_style")):
+            if flag:
+                raise ValueError("%s does nothing without --level_scale" % name)
+        return
+    div = level_scale_list(text)
+    if any(not 1 <= d <= SCALE_MAX_DIVISOR for d in div):
+        raise ValueError("--level_scale: every divisor must lie in 1 .. %d, got %r" % (SCALE_MAX_DIVISOR, text))
+    if any(div[i] > div[i - 1] for i in range(1, 5)):
+        raise ValueError("--level_scale: the divisors must not increase from level 5 to level 1, got %r" % (text,))
+    if div[4] != 1:
+        raise ValueError("--level_scale: the divisor of level 1 must be 1 (the result is made at full size), got %r" % (text,))
+    clash = [name for flag, name in ((args.synthesis, "--synthesis"), (args.maskPath is not None, "--maskPath"),
+                                     (args.interp_styles is not None, "--interp_styles"), (args.weightPath is not None, "--weightPath"),
+                                     (getattr(args, "swap_level", None), "--swap_level")) if flag]
+    if clash:
+        raise ValueError("--level_scale does not mix with %s" % ", ".join(clash))
+    if gain is None:
+        args.scale_detail = SCALE_DETAIL
+    elif not (0.0 <= gain < float("inf")):
+        raise ValueError("--scale_detail: a finite value >= 0 expected, got %r" % (gain,))
+    if coarse is not None and div[0] == 1:
+        raise ValueError("--coarse_style does nothing with --level_scale %s: no level has a divisor > 1" % text)
+
+
+def _scale_once(wct, args, c_f32, style, coarse):
+    """One wct_stylize_scaled of a pair.  --preserve_color match maps each style's colours onto the content first (wct_color_match);
+    with --coarse_style the levels whose divisor is > 1 are prepared from it and the rest from the pair's style, and the cascade runs
+    against those prepared statistics."""
+    div = level_scale_list(args.level_scale)
+    if getattr(args, "preserve_color", None) == "match":
+        style = wct.color_match(style, c_f32)
+        coarse = wct.color_match(coarse, c_f32) if coarse is not None else None
+    if coarse is None:
+        return wct.stylize_scaled(c_f32, style, div, args.scale_detail, args.alpha, args.num_run)
+    reduced = [5 - i for i in range(5) if div[i] > 1]
+    wct.style_prepare(coarse, levels=reduced)
+    wct.style_prepare(style, levels=[L for L in (5, 4, 3, 2, 1) if L not in reduced])
+    res = wct.stylize_scaled(c_f32, None, div, args.scale_detail, args.alpha, args.num_run)
+    wct._scale_keep = (style, coarse)     # the side stream reads both asynchronously
+    return res
+
+
+def _scale_pair(wct, args, logprinter, c_f32, style_f32, coarse_f32):
+    """One pair of --level_scale, and after a clamp of the f16x3 range the same under the exact-fp32 convolutions (`style_f32()` and
+    `coarse_f32()` make the style tensors afresh for it; the resampler and the merge are fp32 and clamp nothing)."""
+    res = _scale_once(wct, args, c_f32, style_f32(), coarse_f32())
+    if wct.saturation_count(reset=True):
+        logprinter("WARNING: f16x3 range exceeded for this pair -> recomputing it with exact-fp32 convolutions")
+        wct.set_conv_mode("fp32")
+        try:
+            res = _scale_once(wct, args, c_f32, style_f32(), coarse_f32())
+            wct.sync()
+        finally:
+            wct.set_conv_mode("f16x3")
+    return res
+
+
+def run_scale(args, wct, pairs, content_dir, style_dir, logprinter) -> float:
+    """--level_scale: the reference's loop with the cascade of wct_stylize_scaled, one pair at a time; returns the summed per-pair time."""
+    import torch
+    from PIL import Image
+    avg = 0.0
+    style_dev = {}
+
+    def on_device(path):
+        u8 = style_dev.get(path)
+        if u8 is None:
+            u8 = torch.from_numpy(load_rgb_u8(path)).pin_memory().cuda(non_blocking=True)
+            style_dev[path] = u8
+            while len(style_dev) > 8:
+                style_dev.pop(next(iter(style_dev)))
+        return u8
+
+    for i, (cfile, sfile) in enumerate(pairs):
+        imname = pair_name(cfile, sfile)
+        logprinter("\n" + "*" * 30 + ' #%s: Transferring "%s" (level divisors %s, detail %g%s)' % (
+            i, imname, args.level_scale, args.scale_detail, ", coarse style %s" % args.coarse_style if args.coarse_style else ""))
+        c_u8 = torch.from_numpy(load_rgb_u8(os.path.join(content_dir, cfile))).pin_memory().cuda(non_blocking=True)
+        s_u8 = on_device(os.path.join(style_dir, sfile))
+        k_u8 = on_device(args.coarse_style) if args.coarse_style else None
+        t0 = time.time()
+        c_f32 = _to_tensor(wct, c_u8, args.content_size)
+        res = _scale_pair(wct, args, logprinter, c_f32, lambda: _to_tensor(wct, s_u8, args.style_size),
+                          lambda: _to_tensor(wct, k_u8, args.style_size) if k_u8 is not None else None)
         out = _finish_u8(wct, args, res, c_f32).cpu().numpy()   # .cpu() syncs
         Image.fromarray(out).save(out_name(args, imname))
         dt = time.time() - t0
@@ -860,6 +987,7 @@ def main(argv: Optional[List[str]] = None) -> int:
     check_smooth_args(args)
     check_transform_args(args)
     check_swap_args(args)
+    check_scale_args(args)
     os.makedirs(args.outf, exist_ok=True)
     logprinter = LogPrinter(args.debug, os.path.join(args.outf, "log_%s_%s.txt" % (args.log_mark, args.mode)))
     logprinter(sorted(vars(args).items()))
@@ -903,6 +1031,13 @@ def main(argv: Optional[List[str]] = None) -> int:
         if args.pipeline > 0:
             logprinter("--pipeline is ignored with --swap_level: patch-swap runs use the serial loop")
         avg = run_swap(args, wct, pairs, content_dir, style_dir, logprinter)
+        if pairs:
+            logprinter("Processed %d images. Average processing time per pair is: %.4f seconds" % (len(pairs), avg / len(pairs)))
+        return 0
+    if args.level_scale:
+        if args.pipeline > 0:
+            logprinter("--pipeline is ignored with --level_scale: scale-controlled runs use the serial loop")
+        avg = run_scale(args, wct, pairs, content_dir, style_dir, logprinter)
         if pairs:
             logprinter("Processed %d images. Average processing time per pair is: %.4f seconds" % (len(pairs), avg / len(pairs)))
         return 0

@@ -57,6 +57,12 @@ SWAP_EPS = 1e-12                                                    # WCT_SWAP_E
 SWAP_KEY_CHUNK = 8192                                               # WCT_SWAP_KEY_CHUNK
 SWAP_LEVELS = (2, 3, 4, 5)
 
+# every symbol include/wct_hip_scale.h declares (scale control: the coarse-to-fine cascade on a device image pyramid); bound from the same libwct_hip.so
+SYMBOLS_SCALE = ["wct_scale_shape", "wct_resample_planar", "wct_pyramid_merge", "wct_stylize_scaled"]
+SCALE_MAX_DIVISOR = 16                                              # WCT_SCALE_MAX_DIVISOR
+SCALE_MAX_SHRINK = 32                                               # WCT_SCALE_MAX_SHRINK
+SCALE_DETAIL = 1.0                                                  # WCT_SCALE_DETAIL
+
 
 class WctLayer(ctypes.Structure):
     _fields_ = [("cin", c_int), ("cout", c_int), ("pool_after", c_int), ("up_after", c_int),
@@ -189,6 +195,10 @@ def load() -> ctypes.CDLL:
     lib.wct_patch_assemble.argtypes = [c_void_p, vp, c_int, c_int, vp, c_int, c_int, c_int, vp, c_float, vp]
     lib.wct_swap_level.argtypes = [c_void_p, c_int, vp, c_int, c_int, vp, c_int, c_int, c_int, c_float, vp, ip, ip]
     lib.wct_stylize_swap.argtypes = [c_void_p, vp, c_int, c_int, vp, c_int, c_int, c_int, c_int, c_float, c_int, vp, ip, ip]
+    lib.wct_scale_shape.argtypes = [c_int, c_int, c_int, ip, ip]
+    lib.wct_resample_planar.argtypes = [c_void_p, vp, c_int, c_int, vp, c_int, c_int, c_int]
+    lib.wct_pyramid_merge.argtypes = [c_void_p, vp, vp, c_int, c_int, vp, c_int, c_int, c_float, vp]
+    lib.wct_stylize_scaled.argtypes = [c_void_p, vp, c_int, c_int, vp, c_int, c_int, c_float, c_int, ip, c_float, vp, ip, ip]
     lib.wct_set_transform.argtypes = [c_void_p, c_int]
     lib.wct_get_transform.argtypes = [c_void_p, ip]
     lib.wct_transform_solve.argtypes = [c_void_p, c_int, c_int, c_double, vp, vp, vp, c_double, vp, vp, ip]

@@ -18,7 +18,7 @@ import ctypes
 import logging
 import os
 from ctypes import c_size_t, byref, c_int, c_void_p
-from typing import Dict, Optional
+from typing import Dict, List, Optional
 
 import numpy as np
 import torch
@@ -995,6 +995,119 @@ class WCT:
         self._chk(self._lib.wct_stylize_swap(self._ctx, c.data_ptr(), H, W, s.data_ptr(), Hs, Ws, int(swap_level), mode, alpha,
                                              int(num_run), out.data_ptr(), byref(ho), byref(wo)))
         self._style_keep = s      # the side stream reads it asynchronously
+        return out.view(-1)[: 3 * ho.value * wo.value].view(1, 3, ho.value, wo.value)
+
+    # ------------------------------------------------------------------ scale control (include/wct_hip_scale.h)
+    @staticmethod
+    def scale_shape(H: int, W: int, divisor: int):
+        """(h_d, w_d) = (16 floor(H / (16 d)), 16 floor(W / (16 d))): the working size of a content of H x W at `divisor`
+        (wct_scale_shape, host only).  ValueError for a divisor outside 1 .. 16 or a working size under 32."""
+        h, w = c_int(), c_int()
+        if _lib.load().wct_scale_shape(int(H), int(W), int(divisor), byref(h), byref(w)) != _lib.WCT_OK:
+            raise ValueError("scale_shape: %d x %d at divisor %r: a divisor in 1 .. %d and a working size of 32 x 32 at least expected"
+                             % (H, W, divisor, _lib.SCALE_MAX_DIVISOR))
+        return h.value, w.value
+
+    @staticmethod
+    def _scale_filter(what: str, filter: str) -> int:
+        if filter not in _lib.RESIZE_FILTERS:
+            raise ValueError("%s: filter must be one of %s, got %r" % (what, ", ".join(repr(f) for f in _lib.RESIZE_FILTERS), filter))
+        return _lib.RESIZE_FILTERS[filter]
+
+    @staticmethod
+    def _scale_sizes(what: str, H: int, W: int, oH: int, oW: int) -> None:
+        if min(H, W, oH, oW) < 1:
+            raise ValueError("%s: empty shape (%d x %d -> %d x %d)" % (what, H, W, oH, oW))
+        if H > _lib.SCALE_MAX_SHRINK * oH or W > _lib.SCALE_MAX_SHRINK * oW:
+            raise ValueError("%s: %d x %d -> %d x %d shrinks an axis by more than %d" % (what, H, W, oH, oW, _lib.SCALE_MAX_SHRINK))
+
+    @torch.no_grad()
+    def resample(self, img: torch.Tensor, size, filter: str = "bicubic", out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The planar fp32 image `img` resampled to size = (oH, oW) with Pillow's bilinear or bicubic weights in floating point
+        (wct_resample_planar): separable, horizontal pass first, fp32 sums in tap order, not clamped, bitwise reproducible; equal
+        sizes are a copy.  `out`: an fp32 tensor on this device with 3*oH*oW values, contiguous, any 4-byte alignment."""
+        f = self._scale_filter("resample", filter)
+        x = self._img(img)
+        H, W, oH, oW = int(x.shape[1]), int(x.shape[2]), int(size[0]), int(size[1])
+        self._scale_sizes("resample", H, W, oH, oW)
+        out = self._out_like(out, "resample", 3 * oH * oW)
+        if out is None:
+            out = torch.empty((1, 3, oH, oW), device=x.device, dtype=torch.float32)
+        self._stream()
+        self._chk(self._lib.wct_resample_planar(self._ctx, x.data_ptr(), H, W, out.data_ptr(), oH, oW, f))
+        return out.view(1, 3, oH, oW)
+
+    @torch.no_grad()
+    def pyramid_merge(self, a: torch.Tensor, b: Optional[torch.Tensor], c: Optional[torch.Tensor], gain: float = _lib.SCALE_DETAIL,
+                      size=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """resample(a - gain * b, c's size, "bicubic") + gain * c in one kernel (wct_pyramid_merge): `a` and `b` at the coarse
+        size, `c` at the fine one.  gain == 0 is resample(a) bit for bit; b and c may then be None and `size` names the result's."""
+        gain = float(gain)
+        if not (0.0 <= gain < float("inf")):
+            raise ValueError("pyramid_merge: gain must be finite and >= 0, got %r" % (gain,))
+        af = self._img(a)
+        hc, wc = int(af.shape[1]), int(af.shape[2])
+        if (b is None or c is None) and gain != 0.0:
+            raise ValueError("pyramid_merge: b and c may be None only with gain == 0")
+        bf = cf = None
+        if b is not None and c is not None:
+            bf, cf = self._img(b), self._img(c)
+            if tuple(bf.shape) != tuple(af.shape):
+                raise ValueError("pyramid_merge: a and b must have one shape, got %s and %s" % (tuple(af.shape), tuple(bf.shape)))
+            if size is not None and (int(size[0]), int(size[1])) != (int(cf.shape[1]), int(cf.shape[2])):
+                raise ValueError("pyramid_merge: size %r is not c's %s" % (size, tuple(cf.shape[1:])))
+            size = (int(cf.shape[1]), int(cf.shape[2]))
+        elif size is None:
+            raise ValueError("pyramid_merge: without b and c the result's size is required")
+        hf, wf = int(size[0]), int(size[1])
+        self._scale_sizes("pyramid_merge", hc, wc, hf, wf)
+        out = self._out_like(out, "pyramid_merge", 3 * hf * wf)
+        if out is None:
+            out = torch.empty((1, 3, hf, wf), device=af.device, dtype=torch.float32)
+        self._stream()
+        self._chk(self._lib.wct_pyramid_merge(self._ctx, af.data_ptr(), bf.data_ptr() if bf is not None else None, hc, wc,
+                                              cf.data_ptr() if cf is not None else None, hf, wf, gain, out.data_ptr()))
+        return out.view(1, 3, hf, wf)
+
+    @staticmethod
+    def _level_div(what: str, level_scale) -> List[int]:
+        div = [int(d) for d in level_scale]
+        if len(div) != 5 or any(int(d) != d for d in level_scale):
+            raise ValueError("%s: five integer divisors expected (levels 5, 4, 3, 2, 1), got %r" % (what, level_scale))
+        if any(not 1 <= d <= _lib.SCALE_MAX_DIVISOR for d in div):
+            raise ValueError("%s: every divisor must lie in 1 .. %d, got %r" % (what, _lib.SCALE_MAX_DIVISOR, div))
+        if any(div[i] > div[i - 1] for i in range(1, 5)) or div[4] != 1:
+            raise ValueError("%s: the divisors must not increase from level 5 to level 1 and must end in 1, got %r" % (what, div))
+        return div
+
+    @torch.no_grad()
+    def stylize_scaled(self, contentImg: torch.Tensor, styleImg: Optional[torch.Tensor], level_scale, detail_gain: float = _lib.SCALE_DETAIL,
+                       alpha: Optional[float] = None, num_run: int = 1, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The 5 -> 1 cascade with level L run on the content reduced by level_scale[5 - L] (divisors of levels 5, 4, 3, 2, 1, e.g.
+        (4, 4, 2, 1, 1)), one library call (wct_stylize_scaled): where the divisor changes, the running image is brought to the next
+        working size by pyramid_merge(cur, content at the old size, content at the new size, detail_gain).  Bit-identical to the
+        composition of resample / pyramid_merge / style_transfer_level; all divisors 1 is stylize().  styleImg=None runs against
+        the statistics already in the context (style_prepare per level set = scale mixing), which then survive the call."""
+        div = self._level_div("stylize_scaled", level_scale)
+        detail_gain = float(detail_gain)
+        if not (0.0 <= detail_gain < float("inf")):
+            raise ValueError("stylize_scaled: detail_gain must be finite and >= 0, got %r" % (detail_gain,))
+        alpha = self.alpha if alpha is None else float(alpha)
+        c = self._img(contentImg)
+        H, W = int(c.shape[1]), int(c.shape[2])
+        for d in sorted(set(div)):
+            self.scale_shape(H, W, d)
+        s, Hs, Ws = None, 0, 0
+        if styleImg is not None:
+            s = self._img(styleImg)
+            Hs, Ws = int(s.shape[1]), int(s.shape[2])
+        out = self._out_image(out, H, W)
+        ho, wo = c_int(), c_int()
+        self._stream()
+        self._chk(self._lib.wct_stylize_scaled(self._ctx, c.data_ptr(), H, W, s.data_ptr() if s is not None else None, Hs, Ws, alpha,
+                                               int(num_run), (c_int * 5)(*div), detail_gain, out.data_ptr(), byref(ho), byref(wo)))
+        if s is not None:
+            self._style_keep = s      # the side stream reads it asynchronously
         return out.view(-1)[: 3 * ho.value * wo.value].view(1, 3, ho.value, wo.value)
 
     # ------------------------------------------------------------------ spatial control (regions)
