@@ -3,6 +3,7 @@
 // in the kernels of conv3x3.hip / moments.hip / solve.hip / misc.hip.
 #include "../../include/wct_hip.h"
 #include "../../include/wct_hip_color.h"
+#include "../../include/wct_hip_guided.h"
 #include "../../include/wct_hip_scale.h"
 #include "../../include/wct_hip_smooth.h"
 #include "../../include/wct_hip_swap.h"
@@ -172,6 +173,12 @@ struct wct_ctx {
   // the transformed feature map, the kernels' workspaces; pinned [6][256] label histograms read back once per call
   DevBuf eigR[8][6], eigCR[8], regLab, regHist, regSums, regMb, regFeat, wsRegMom, wsRegApply;
   unsigned* reg_hist_host = nullptr;
+  // region-to-region transfer (include/wct_hip_guided.h).  wct_stylize_guided: the mapped styles' level label maps and histograms (made on
+  // the caller's stream in the pre-pass), and the SIDE lane's own per-label sums and moments workspace -- the main lane's regSums / wsRegMom
+  // are in use at the same time; pinned [8][6][256] style histograms read back with the content's.  K-means: the two encoded maps, the
+  // kernels' partials, and [sh_c C | sc_c C | sh_s C | sc_s C | centroids 2 K C | n K | sum K C | cost 1 | idx K | lab_c | lab_s]
+  DevBuf gdLab, gdHist, gdSums, wsGdMom, kmFeatC, kmFeatS, kmWs, kmStat;
+  unsigned* gd_hist_host = nullptr;
   // style interpolation / weights (wct_stylize_interp, wct_style_blend, wct_stylize_blend): the pooled level weight maps, (V1, V2) per
   // (level, k) + the weight check's counts, the pooling workspace, the mixed apply's workspace; pinned copy of blendStat read back once
   // per wct_stylize_blend call (the regions' moments / maps / feature buffers are reused)
@@ -193,8 +200,9 @@ struct wct_ctx {
     for (DevBuf* b : {&featS, &tmpT, &wsAsm, &trBuf, &small, &foldW, &foldW16, &eigC, &u8c, &u8s, &u8o, &rsz_tmp, &noise, &colStyle, &colOut, &colWs, &smSums, &smAB, &swFc, &swFs, &swQ, &swK, &swOut, &swIdx, &swRun, &swNorm, &swLab, &packed,
                       &shIn, &shOut, &shNext, &shEdge, &shStyle, &shStats, &shMb,
                       &regLab, &regHist, &regSums, &regMb, &regFeat, &wsRegMom, &wsRegApply,
-                      &blendW, &blendStat, &wsBlendPool, &wsBlendApply})
+                      &blendW, &blendStat, &wsBlendPool, &wsBlendApply, &gdLab, &gdHist, &kmFeatC, &kmFeatS, &kmWs, &kmStat})
       f(*b, &main, true);
+    for (DevBuf* b : {&gdSums, &wsGdMom}) f(*b, &side, true);   // the guided call's style side
     for (DevBuf& b : scF) f(b, &main, true);
     f(scStage, &main, true);
     f(scTab, &main, true);
@@ -1253,6 +1261,7 @@ void wct_destroy(wct_ctx* ctx) {
   if (ctx->ev_switch) (void)hipEventDestroy(ctx->ev_switch);
   if (ctx->reg_hist_host) (void)hipHostFree(ctx->reg_hist_host);
   if (ctx->blend_host) (void)hipHostFree(ctx->blend_host);
+  if (ctx->gd_hist_host) (void)hipHostFree(ctx->gd_hist_host);
 
   if (ctx->side.stream) (void)hipStreamDestroy(ctx->side.stream);
   if (ctx->sat_dev) (void)hipFree(ctx->sat_dev);
@@ -2681,16 +2690,168 @@ int multi_style_level(wct_ctx* ctx, const char* what, int level, const float* im
   return WCT_OK;
 }
 
-// one level of the regions cascade: per-label moments, a region with fewer than 2 pixels keeps its features, per-label apply
-int regions_level(wct_ctx* ctx, int level, const float* img, int H, int W, const RegionPlan& pl, int K, const float* alpha, float* dst, int* ho, int* wo) {
+// The style half of the guidance (include/wct_hip_guided.h): which style image region k is transformed against, and for a style with a
+// label map its level maps (gdLab, element lab_off[s] + off[L]) and per-(level, label) pixel counts.  wct_stylize_regions is the case
+// without maps and with region_style[k] = k.
+struct StyleMapPlan {
+  int h[6], w[6];
+  size_t off[6];
+  unsigned cnt[6][256];
+};
+
+struct GuidedStyles {
+  int S = 0;
+  const float* const* styles = nullptr;
+  const int *Hs = nullptr, *Ws = nullptr;
+  const uint8_t* const* maps = nullptr;     // null: no style has a map
+  const int* region_style = nullptr;        // null: region k against style k
+  bool any_mapped = false;
+  std::vector<StyleMapPlan> plan;           // [S], filled for the mapped styles
+  size_t lab_off[REG_MAX] = {};
+  int style_of(int k) const { return region_style ? region_style[k] : k; }
+  bool mapped(int s) const { return maps && maps[s]; }
+  // style pixels behind region k at `level`: the whole image (always >= 2 where its encoder runs) or its label k
+  double style_n(int level, int k) const {
+    const int s = style_of(k);
+    return mapped(s) ? (double)plan[s].cnt[level][k] : 2.0;
+  }
+};
+
+// one level of the regions cascade: per-label moments, a region with fewer than 2 content or style pixels keeps its features, per-label apply
+int regions_level(wct_ctx* ctx, int level, const float* img, int H, int W, const RegionPlan& pl, const GuidedStyles& g, int K, const float* alpha,
+                  float* dst, int* ho, int* wo) {
   const uint8_t* lab = reinterpret_cast<const uint8_t*>(ctx->regLab.p) + pl.off[level];
   return multi_style_level(
       ctx, "regions", level, img, H, W, pl, K, alpha, true, dst, ho, wo,
       [&](const float* fC, int C, int h, int w, double* n, double* sum, double* sumsq) {
         return moments_labeled_impl(ctx, ctx->main, fC, C, h, w, lab, K, n, sum, sumsq);
       },
-      [&](int k) -> double { return pl.cnt[level][k]; },
+      [&](int k) -> double { return g.style_n(level, k) < 2 ? 0.0 : (double)pl.cnt[level][k]; },
       [&](const float* fC, int C, long npix, const double* M, const double* b, float* fO) { return apply_labeled_impl(ctx, fC, C, npix, lab, K, M, b, fO); });
+}
+
+// The style side of one level of a regions / guided call.  Unmapped styles: style_side into slot k, region by region, as ever.  A mapped
+// style that a region names: encoded ONCE into featS (fp32 NHWC at every level: the fused level-1 moments keep no feature map), its
+// per-label moments over its level map into gdSums with the side lane's OWN workspace (the main lane's moments_labeled_impl is using
+// regSums / wsRegMom meanwhile), then one matrix square root per region naming it, with that region's style pixel count.
+int guided_style_side(wct_ctx* ctx, int level, int K, const GuidedStyles& g) {
+  for (int k = 0; k < K; ++k) {
+    const int s = g.style_of(k);
+    if (!g.mapped(s))
+      if (int rc = style_side(ctx, level, g.styles[s], g.Hs[s], g.Ws[s], k)) return rc;
+  }
+  if (!g.any_mapped) return WCT_OK;
+  Module& me = ctx->mod[WCT_KIND_ENC][level];
+  if (!me.loaded) return fail(ctx, WCT_ERR_STATE, "encoder %d not loaded", level);
+  const int C = me.layers.back().d.cout;
+  const size_t cc = (size_t)C * C;
+  Lane& ln = ctx->overlap ? ctx->side : ctx->main;
+  for (int s = 0; s < g.S; ++s) {
+    if (!g.mapped(s)) continue;
+    bool named = false;
+    for (int k = 0; k < K; ++k) named = named || g.style_of(k) == s;
+    if (!named) continue;
+    const StyleMapPlan& sp = g.plan[s];
+    const int hs = sp.h[level], ws = sp.w[level];
+    const long npix = (long)hs * ws;
+    if (int rc = ensure(ctx, ctx->featS, (size_t)npix * C * sizeof(float))) return rc;
+    if (int rc = ensure(ctx, ctx->gdSums, (size_t)K * (1 + C + cc) * sizeof(double))) return rc;
+    if (int rc = ensure(ctx, ctx->wsGdMom, moments_labeled_workspace_bytes(C, npix, K))) return rc;
+    SumsView sv;
+    if (int rc = sums_view(ctx, ln, sv)) return rc;
+    float* fS = reinterpret_cast<float*>(ctx->featS.p);
+    double* n = reinterpret_cast<double*>(ctx->gdSums.p);
+    double* sum = n + K;
+    double* sumsq = sum + (size_t)K * C;
+    const uint8_t* lab = reinterpret_cast<const uint8_t*>(ctx->gdLab.p) + g.lab_off[s] + sp.off[level];
+    if (int rc = encode_impl(ctx, ln, level, g.styles[s], g.Hs[s], g.Ws[s], fS, nullptr, nullptr)) return rc;
+    {
+      ProfScope ps(ctx, ln.stream, "moments_labeled", 2.0 * C * C * npix, 4.0 * C * npix + (double)K * npix);
+      HIPCHK(ctx, launch_moments_labeled(fS, C, npix, lab, K, n, sum, sumsq, ctx->wsGdMom.p, ctx->wsGdMom.cap, ln.stream, mom32_on(ctx, npix)));
+    }
+    for (int k = 0; k < K; ++k)
+      if (g.style_of(k) == s && sp.cnt[level][k] >= 2)
+        if (int rc = eig_impl(ctx, ln, C, (double)sp.cnt[level][k], sum + (size_t)k * C, sumsq + k * cc, 0, ctx->eigR[k][level], sv.info + 1)) return rc;
+  }
+  HIPCHK(ctx, hipEventRecord(ctx->ev_style[level], ln.stream));
+  return WCT_OK;
+}
+
+// wct_stylize_regions and wct_stylize_guided: ONE path.  `what` names the entry in a refusal.
+int regions_cascade(wct_ctx* ctx, const char* what, const float* content, int H, int W, const uint8_t* labels, int K, GuidedStyles& g,
+                    const float* alpha, int num_run, float* out, int* Ho, int* Wo) {
+  for (int level = 1; level <= 5; ++level)
+    if (!ctx->mod[WCT_KIND_ENC][level].loaded || !ctx->mod[WCT_KIND_DEC][level].loaded) return fail(ctx, WCT_ERR_STATE, "%s: level %d not loaded", what, level);
+  if (H < 32 || W < 32) return fail(ctx, WCT_ERR_INVALID, "%s: content %dx%d too small for level 5", what, H, W);
+  // label maps of the five levels + their histograms, read back ONCE: the solvers take each region's pixel count on the host, and the
+  // labels are checked before anything is written to `out`
+  RegionPlan pl{};
+  const size_t total = level_geom(pl, H, W, 1, 256);
+  if (int rc = ensure(ctx, ctx->regLab, total)) return rc;
+  if (int rc = ensure(ctx, ctx->regHist, 6 * 256 * sizeof(unsigned))) return rc;
+  if (!ctx->reg_hist_host) HIPCHK(ctx, hipHostMalloc(reinterpret_cast<void**>(&ctx->reg_hist_host), 6 * 256 * sizeof(unsigned), hipHostMallocDefault));
+  // the mapped styles' geometry: the style is not cropped, level L's map is floor(Hs / 2^(L-1)) x floor(Ws / 2^(L-1)) (level_dims)
+  size_t stotal = 0;
+  if (g.any_mapped) {
+    g.plan.assign(g.S, StyleMapPlan{});
+    for (int s = 0; s < g.S; ++s) {
+      if (!g.mapped(s)) continue;
+      if (g.Hs[s] < 32 || g.Ws[s] < 32) return fail(ctx, WCT_ERR_INVALID, "%s: mapped style %d is %dx%d, too small for level 5", what, s, g.Hs[s], g.Ws[s]);
+      g.lab_off[s] = stotal;
+      size_t off = 0;
+      for (int level = 5; level >= 1; --level) {
+        level_dims(level, g.Hs[s], g.Ws[s], g.plan[s].h[level], g.plan[s].w[level]);
+        g.plan[s].off[level] = off;
+        off += ((size_t)g.plan[s].h[level] * g.plan[s].w[level] + 255) & ~(size_t)255;
+      }
+      stotal += off;
+    }
+    if (int rc = ensure(ctx, ctx->gdLab, stotal)) return rc;
+    if (int rc = ensure(ctx, ctx->gdHist, (size_t)REG_MAX * 6 * 256 * sizeof(unsigned))) return rc;
+    if (!ctx->gd_hist_host)
+      HIPCHK(ctx, hipHostMalloc(reinterpret_cast<void**>(&ctx->gd_hist_host), (size_t)REG_MAX * 6 * 256 * sizeof(unsigned), hipHostMallocDefault));
+  }
+  uint8_t* maps[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  for (int level = 1; level <= 5; ++level) maps[level] = reinterpret_cast<uint8_t*>(ctx->regLab.p) + pl.off[level];
+  unsigned* hist = reinterpret_cast<unsigned*>(ctx->regHist.p);
+  {
+    ProfScope ps(ctx, ctx->main.stream, "labels_levels", 0, (double)H * W + 2.0 * total);
+    HIPCHK(ctx, launch_labels_levels(labels, H, W, pl.h, pl.w, maps, hist, ctx->main.stream));
+  }
+  HIPCHK(ctx, hipMemcpyAsync(ctx->reg_hist_host, hist, 6 * 256 * sizeof(unsigned), hipMemcpyDeviceToHost, ctx->main.stream));
+  if (g.any_mapped) {
+    for (int s = 0; s < g.S; ++s) {
+      if (!g.mapped(s)) continue;
+      uint8_t* smaps[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+      for (int level = 1; level <= 5; ++level) smaps[level] = reinterpret_cast<uint8_t*>(ctx->gdLab.p) + g.lab_off[s] + g.plan[s].off[level];
+      unsigned* shist = reinterpret_cast<unsigned*>(ctx->gdHist.p) + (size_t)s * 6 * 256;
+      ProfScope ps(ctx, ctx->main.stream, "labels_levels", 0, (double)g.Hs[s] * g.Ws[s]);
+      HIPCHK(ctx, launch_labels_levels(g.maps[s], g.Hs[s], g.Ws[s], g.plan[s].h, g.plan[s].w, smaps, shist, ctx->main.stream));
+    }
+    HIPCHK(ctx, hipMemcpyAsync(ctx->gd_hist_host, ctx->gdHist.p, (size_t)g.S * 6 * 256 * sizeof(unsigned), hipMemcpyDeviceToHost, ctx->main.stream));
+  }
+  HIPCHK(ctx, hipStreamSynchronize(ctx->main.stream));
+  memcpy(pl.cnt, ctx->reg_hist_host, sizeof pl.cnt);
+  for (int v = K; v < 255; ++v)
+    if (pl.cnt[0][v])
+      return fail(ctx, WCT_ERR_INVALID, "%s: label value %d (%u pixels) is neither a region 0..%d nor 255 (unstyled)", what, v, pl.cnt[0][v], K - 1);
+  for (int s = 0; s < g.S && g.any_mapped; ++s) {
+    if (!g.mapped(s)) continue;
+    memcpy(g.plan[s].cnt, ctx->gd_hist_host + (size_t)s * 6 * 256, sizeof g.plan[s].cnt);
+    for (int v = K; v < 255; ++v)
+      if (g.plan[s].cnt[0][v])
+        return fail(ctx, WCT_ERR_INVALID, "%s: style %d label value %d (%u pixels) is neither a region 0..%d nor 255 (unused)", what, s, v,
+                    g.plan[s].cnt[0][v], K - 1);
+  }
+  if (int rc = with_deferred_solves(ctx, false, [&]() -> int {
+        if (int rc = fork_side(ctx)) return rc;
+        if (int rc = guided_style_side(ctx, 5, K, g)) return rc;
+        return run_cascade(
+            ctx, content, H, W, num_run, out, Ho, Wo,
+            [&](int level, const float* cur, int h, int w, float* dst, int* ho, int* wo) { return regions_level(ctx, level, cur, h, w, pl, g, K, alpha, dst, ho, wo); },
+            [&](int level) { return guided_style_side(ctx, level - 1, K, g); });
+      })) return rc;
+  return range_readback(ctx);
 }
 }  // namespace
 
@@ -2728,37 +2889,136 @@ int wct_stylize_regions(wct_ctx* ctx, const float* content, int H, int W, const 
     if (!styles[k]) return fail(ctx, WCT_ERR_INVALID, "stylize_regions: style %d is NULL", k);
     if (!std::isfinite(alpha[k])) return fail(ctx, WCT_ERR_INVALID, "stylize_regions: alpha[%d] is not finite", k);
   }
-  for (int level = 1; level <= 5; ++level)
-    if (!ctx->mod[WCT_KIND_ENC][level].loaded || !ctx->mod[WCT_KIND_DEC][level].loaded) return fail(ctx, WCT_ERR_STATE, "stylize_regions: level %d not loaded", level);
-  if (H < 32 || W < 32) return fail(ctx, WCT_ERR_INVALID, "stylize_regions: content %dx%d too small for level 5", H, W);
-  // label maps of the five levels + their histograms, read back ONCE: the solvers take each region's pixel count on the host, and the
-  // labels are checked before anything is written to `out`
-  RegionPlan pl{};
-  const size_t total = level_geom(pl, H, W, 1, 256);
-  if (int rc = ensure(ctx, ctx->regLab, total)) return rc;
-  if (int rc = ensure(ctx, ctx->regHist, 6 * 256 * sizeof(unsigned))) return rc;
-  if (!ctx->reg_hist_host) HIPCHK(ctx, hipHostMalloc(reinterpret_cast<void**>(&ctx->reg_hist_host), 6 * 256 * sizeof(unsigned), hipHostMallocDefault));
-  uint8_t* maps[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  for (int level = 1; level <= 5; ++level) maps[level] = reinterpret_cast<uint8_t*>(ctx->regLab.p) + pl.off[level];
-  unsigned* hist = reinterpret_cast<unsigned*>(ctx->regHist.p);
-  {
-    ProfScope ps(ctx, ctx->main.stream, "labels_levels", 0, (double)H * W + 2.0 * total);
-    HIPCHK(ctx, launch_labels_levels(labels, H, W, pl.h, pl.w, maps, hist, ctx->main.stream));
+  GuidedStyles g;
+  g.S = K; g.styles = styles; g.Hs = Hs; g.Ws = Ws;
+  return regions_cascade(ctx, "stylize_regions", content, H, W, labels, K, g, alpha, num_run, out, Ho, Wo);
+}
+
+int wct_stylize_guided(wct_ctx* ctx, const float* content, int H, int W, const uint8_t* labels, int K, int S, const float* const* styles,
+                       const int* Hs, const int* Ws, const uint8_t* const* style_labels, const int* region_style, const float* alpha,
+                       int num_run, float* out, int* Ho, int* Wo) {
+  if (!ctx) return WCT_ERR_INVALID;
+  WCT_GUARD(ctx);
+  if (ctx->transform != WCT_TRANSFORM_WCT) return fail(ctx, WCT_ERR_INVALID, "stylize_guided: defined for the wct transform only (wct_set_transform)");
+  if (!content || !labels || !styles || !Hs || !Ws || !style_labels || !region_style || !alpha || !out || num_run < 1)
+    return fail(ctx, WCT_ERR_INVALID, "stylize_guided: bad arguments");
+  if (K < 1 || K > WCT_GUIDED_MAX_REGIONS) return fail(ctx, WCT_ERR_INVALID, "stylize_guided: K=%d outside [1, %d]", K, WCT_GUIDED_MAX_REGIONS);
+  if (S < 1 || S > WCT_GUIDED_MAX_STYLES) return fail(ctx, WCT_ERR_INVALID, "stylize_guided: S=%d outside [1, %d]", S, WCT_GUIDED_MAX_STYLES);
+  GuidedStyles g;
+  g.S = S; g.styles = styles; g.Hs = Hs; g.Ws = Ws; g.maps = style_labels; g.region_style = region_style;
+  for (int s = 0; s < S; ++s) {
+    if (!styles[s]) return fail(ctx, WCT_ERR_INVALID, "stylize_guided: style %d is NULL", s);
+    g.any_mapped = g.any_mapped || style_labels[s] != nullptr;
   }
-  HIPCHK(ctx, hipMemcpyAsync(ctx->reg_hist_host, hist, 6 * 256 * sizeof(unsigned), hipMemcpyDeviceToHost, ctx->main.stream));
-  HIPCHK(ctx, hipStreamSynchronize(ctx->main.stream));
-  memcpy(pl.cnt, ctx->reg_hist_host, sizeof pl.cnt);
-  for (int v = K; v < 255; ++v)
-    if (pl.cnt[0][v])
-      return fail(ctx, WCT_ERR_INVALID, "stylize_regions: label value %d (%u pixels) is neither a region 0..%d nor 255 (unstyled)", v, pl.cnt[0][v], K - 1);
-  if (int rc = with_deferred_solves(ctx, false, [&]() -> int {
-        if (int rc = fork_side(ctx)) return rc;
-        if (int rc = style_side_slots(ctx, 5, K, styles, Hs, Ws)) return rc;
-        return run_cascade(
-            ctx, content, H, W, num_run, out, Ho, Wo,
-            [&](int level, const float* cur, int h, int w, float* dst, int* ho, int* wo) { return regions_level(ctx, level, cur, h, w, pl, K, alpha, dst, ho, wo); },
-            [&](int level) { return style_side_slots(ctx, level - 1, K, styles, Hs, Ws); });
-      })) return rc;
+  for (int k = 0; k < K; ++k) {
+    if (region_style[k] < 0 || region_style[k] >= S) return fail(ctx, WCT_ERR_INVALID, "stylize_guided: region_style[%d]=%d outside [0, %d)", k, region_style[k], S);
+    if (!std::isfinite(alpha[k])) return fail(ctx, WCT_ERR_INVALID, "stylize_guided: alpha[%d] is not finite", k);
+  }
+  return regions_cascade(ctx, "stylize_guided", content, H, W, labels, K, g, alpha, num_run, out, Ho, Wo);
+}
+
+}  // extern "C"
+
+// ---- k-means on feature maps (include/wct_hip_guided.h; kernels in cluster.hip) ---------------------------------------------------------
+namespace {
+int kmeans_args(wct_ctx* ctx, const char* what, int C, int h, int w, int K) {
+  if (C < 4 || (C & 3) || C > 512) return fail(ctx, WCT_ERR_INVALID, "%s: C=%d must be a multiple of 4 in [4,512]", what, C);
+  if (h < 1 || w < 1 || (long)h * w >= (1L << 31)) return fail(ctx, WCT_ERR_INVALID, "%s: bad map %dx%d", what, h, w);
+  if (K < 1 || K > WCT_KMEANS_MAX_K) return fail(ctx, WCT_ERR_INVALID, "%s: K=%d outside [1, %d]", what, K, WCT_KMEANS_MAX_K);
+  return WCT_OK;
+}
+
+int kmeans_assign_impl(wct_ctx* ctx, const float* feat, int C, long npix, const double* shift, const double* scale, const double* cent, int K,
+                       uint8_t* labels, double* n, double* sum, double* cost, double* next) {
+  if (int rc = ensure(ctx, ctx->kmWs, kmeans_assign_workspace_bytes(C, npix, K))) return rc;
+  ProfScope ps(ctx, ctx->main.stream, "kmeans_assign", 3.0 * K * C * npix, 4.0 * C * npix);
+  HIPCHK(ctx, launch_kmeans_assign(feat, C, npix, shift, scale, cent, K, labels, n, sum, cost, next, ctx->kmWs.p, ctx->kmWs.cap, ctx->main.stream));
+  return WCT_OK;
+}
+
+int kmeans_seed_impl(wct_ctx* ctx, const float* feat, int C, long npix, const double* shift, const double* scale, int K, double* cent, int* idx) {
+  if (int rc = ensure(ctx, ctx->kmWs, kmeans_seed_workspace_bytes(npix))) return rc;
+  ProfScope ps(ctx, ctx->main.stream, "kmeans_seed", 3.0 * K * C * npix, 4.0 * K * C * npix);
+  HIPCHK(ctx, launch_kmeans_seed(feat, C, npix, shift, scale, K, cent, idx, ctx->kmWs.p, ctx->kmWs.cap, ctx->main.stream));
+  return WCT_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int wct_kmeans_assign(wct_ctx* ctx, const float* feat, int C, int h, int w, const double* shift, const double* scale, const double* centroids,
+                      int K, uint8_t* labels, double* n, double* sum, double* cost, double* next) {
+  if (!ctx) return WCT_ERR_INVALID;
+  WCT_GUARD(ctx);
+  if (!feat || !shift || !scale || !centroids || !n || !sum || !cost) return fail(ctx, WCT_ERR_INVALID, "kmeans_assign: NULL pointer");
+  if (reinterpret_cast<uintptr_t>(feat) & 15) return fail(ctx, WCT_ERR_INVALID, "kmeans_assign: the map must be 16-byte aligned");
+  if (int rc = kmeans_args(ctx, "kmeans_assign", C, h, w, K)) return rc;
+  return kmeans_assign_impl(ctx, feat, C, (long)h * w, shift, scale, centroids, K, labels, n, sum, cost, next);
+}
+
+int wct_kmeans_seed(wct_ctx* ctx, const float* feat, int C, int h, int w, const double* shift, const double* scale, int K, double* centroids,
+                    int* idx) {
+  if (!ctx) return WCT_ERR_INVALID;
+  WCT_GUARD(ctx);
+  if (!feat || !shift || !scale || !centroids || !idx) return fail(ctx, WCT_ERR_INVALID, "kmeans_seed: NULL pointer");
+  if (reinterpret_cast<uintptr_t>(feat) & 15) return fail(ctx, WCT_ERR_INVALID, "kmeans_seed: the map must be 16-byte aligned");
+  if (int rc = kmeans_args(ctx, "kmeans_seed", C, h, w, K)) return rc;
+  return kmeans_seed_impl(ctx, feat, C, (long)h * w, shift, scale, K, centroids, idx);
+}
+
+int wct_feature_regions(wct_ctx* ctx, int level, const float* content, int H, int W, const float* style, int Hs, int Ws, int K, int iters,
+                        uint8_t* labels_c, uint8_t* labels_s, double* centroids_out) {
+  if (!ctx) return WCT_ERR_INVALID;
+  WCT_GUARD(ctx);
+  if (!content || !style || !labels_c || !labels_s) return fail(ctx, WCT_ERR_INVALID, "feature_regions: NULL pointer");
+  if (level < 2 || level > 5) return fail(ctx, WCT_ERR_INVALID, "feature_regions: level %d outside 2..5", level);
+  if (iters < 1 || iters > WCT_KMEANS_MAX_ITERS) return fail(ctx, WCT_ERR_INVALID, "feature_regions: iters=%d outside [1, %d]", iters, WCT_KMEANS_MAX_ITERS);
+  Module& me = ctx->mod[WCT_KIND_ENC][level];
+  if (!me.loaded) return fail(ctx, WCT_ERR_STATE, "feature_regions: encoder %d not loaded", level);
+  const int C = me.layers.back().d.cout;
+  const int smin = 2 << (level - 1);
+  if (H < smin || W < smin || Hs < smin || Ws < smin)
+    return fail(ctx, WCT_ERR_INVALID, "feature_regions: images %dx%d / %dx%d too small for level %d", H, W, Hs, Ws, level);
+  int h, w, hs, ws;
+  level_dims(level, H, W, h, w);
+  level_dims(level, Hs, Ws, hs, ws);
+  if (int rc = kmeans_args(ctx, "feature_regions", C, h, w, K)) return rc;
+  if (int rc = kmeans_args(ctx, "feature_regions", C, hs, ws, K)) return rc;
+  Lane& ln = ctx->main;
+  const long np = (long)h * w, nps = (long)hs * ws;
+  const size_t kc = (size_t)K * C;
+  if (int rc = ensure(ctx, ctx->kmFeatC, (size_t)np * C * sizeof(float))) return rc;
+  if (int rc = ensure(ctx, ctx->kmFeatS, (size_t)nps * C * sizeof(float))) return rc;
+  // [sh_c C | sc_c C | sh_s C | sc_s C | centroids 2 K C | n K | sum K C | cost 1] fp64, then idx K int32 (padded), lab_c, lab_s
+  const size_t nd = 4 * (size_t)C + 2 * kc + K + kc + 1, idx_off = nd * sizeof(double), labc_off = idx_off + 64, labs_off = labc_off + (((size_t)np + 255) & ~(size_t)255);
+  if (int rc = ensure(ctx, ctx->kmStat, labs_off + (size_t)nps)) return rc;
+  if (int rc = ensure(ctx, ctx->kmWs, std::max({kmeans_seed_workspace_bytes(nps), kmeans_assign_workspace_bytes(C, nps, K), kmeans_assign_workspace_bytes(C, np, K)})))
+    return rc;   // once for the whole call: a growing workspace would synchronise between the passes
+  SumsView sv;
+  if (int rc = sums_view(ctx, ln, sv)) return rc;
+  float* fC = reinterpret_cast<float*>(ctx->kmFeatC.p);
+  float* fS = reinterpret_cast<float*>(ctx->kmFeatS.p);
+  double* st = reinterpret_cast<double*>(ctx->kmStat.p);
+  double *sh_c = st, *sc_c = st + C, *sh_s = st + 2 * C, *sc_s = st + 3 * C, *cent = st + 4 * C;
+  double *n = cent + 2 * kc, *sum = n + K, *cost = sum + kc;
+  int* idx = reinterpret_cast<int*>(reinterpret_cast<char*>(ctx->kmStat.p) + idx_off);
+  uint8_t* lab_c = reinterpret_cast<uint8_t*>(ctx->kmStat.p) + labc_off;
+  uint8_t* lab_s = reinterpret_cast<uint8_t*>(ctx->kmStat.p) + labs_off;
+  if (int rc = encode_impl(ctx, ln, level, content, H, W, fC, nullptr, nullptr)) return rc;
+  if (int rc = moments_impl(ctx, ln, fC, C, h, w, 0, w, sv.sum, sv.sumsq)) return rc;
+  HIPCHK(ctx, launch_kmeans_standardise(sv.sum, sv.sumsq, C, (double)np, sh_c, sc_c, ln.stream));
+  if (int rc = encode_impl(ctx, ln, level, style, Hs, Ws, fS, nullptr, nullptr)) return rc;
+  if (int rc = moments_impl(ctx, ln, fS, C, hs, ws, 0, ws, sv.sum, sv.sumsq)) return rc;
+  HIPCHK(ctx, launch_kmeans_standardise(sv.sum, sv.sumsq, C, (double)nps, sh_s, sc_s, ln.stream));
+  if (int rc = kmeans_seed_impl(ctx, fS, C, nps, sh_s, sc_s, K, cent, idx)) return rc;
+  for (int it = 0; it < iters; ++it)
+    if (int rc = kmeans_assign_impl(ctx, fS, C, nps, sh_s, sc_s, cent + (it & 1) * kc, K, nullptr, n, sum, cost, cent + ((it + 1) & 1) * kc)) return rc;
+  const double* fin = cent + (iters & 1) * kc;
+  if (int rc = kmeans_assign_impl(ctx, fS, C, nps, sh_s, sc_s, fin, K, lab_s, n, sum, cost, nullptr)) return rc;
+  if (int rc = kmeans_assign_impl(ctx, fC, C, np, sh_c, sc_c, fin, K, lab_c, n, sum, cost, nullptr)) return rc;
+  HIPCHK(ctx, launch_kmeans_expand(lab_s, hs, ws, level, labels_s, Hs, Ws, ln.stream));
+  HIPCHK(ctx, launch_kmeans_expand(lab_c, h, w, level, labels_c, H, W, ln.stream));
+  if (centroids_out) HIPCHK(ctx, hipMemcpyAsync(centroids_out, fin, kc * sizeof(double), hipMemcpyDeviceToDevice, ln.stream));
   return range_readback(ctx);
 }
 

@@ -285,6 +285,21 @@ hipError_t launch_apply_labeled(const float* feat, int C, long npix, const uint8
                                 float* out, void* workspace, size_t workspace_bytes, hipStream_t s);
 hipError_t launch_mb_identity(double* M, double* b, int C, int K, unsigned mask, hipStream_t s);
 
+// ---- k-means on NHWC fp32 feature maps (cluster.hip; include/wct_hip_guided.h); C a multiple of 4 in 4 .. 512, K <= 8, npix < 2^31
+//   launch_kmeans_assign       one Lloyd step: labels (may be null), n[K], sum[K][C] (of the standardised z), cost[1], next (may be null)
+//   launch_kmeans_seed         the farthest-first start: cent[K][C], idx[K]
+//   launch_kmeans_standardise  shift = mean, scale = 1 / sqrt(population variance) (0 for a dead channel) from raw moments of n pixels
+//   launch_kmeans_expand       out[y][x] = lab[min(y >> (level-1), h-1)][min(x >> (level-1), w-1)]
+size_t kmeans_assign_workspace_bytes(int C, long npix, int K);
+hipError_t launch_kmeans_assign(const float* feat, int C, long npix, const double* shift, const double* scale, const double* cent, int K,
+                                uint8_t* labels, double* n, double* sum, double* cost, double* next, void* workspace, size_t workspace_bytes,
+                                hipStream_t s);
+size_t kmeans_seed_workspace_bytes(long npix);
+hipError_t launch_kmeans_seed(const float* feat, int C, long npix, const double* shift, const double* scale, int K, double* cent, int* idx,
+                              void* workspace, size_t workspace_bytes, hipStream_t s);
+hipError_t launch_kmeans_standardise(const double* sum, const double* sumsq, int C, double n, double* shift, double* scale, hipStream_t s);
+hipError_t launch_kmeans_expand(const uint8_t* lab, int h, int w, int level, uint8_t* out, int H, int W, hipStream_t s);
+
 // ---- style interpolation and per-pixel style weights (blend.hip); K <= 8
 //   launch_stats_blend       Fo = sum_k lam[k] F[k], muo = sum_k lam[k] mu[k] (C x C and C doubles; device pointers in host arrays), fixed
 //                            k order: lam = (1, 0, ...) reproduces slot 0 bit for bit

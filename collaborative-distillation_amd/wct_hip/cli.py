@@ -41,6 +41,9 @@ features (--swap_match whitened, the default) or on the features themselves (raw
 divisor dL and, where the working size grows, brings the running image up and puts the content's fine detail back (--scale_detail, a look);
 --coarse_style gives the reduced levels a style of their own (scale mixing).  One pair at a time (wct_stylize_scaled, the serial loop);
 --transform, --preserve_color and --smooth_radius go with it through the public calls around it.  The files carry _scale=<d5-d4-d3-d2-d1>.
+--styleMaskPath DIR (with --maskPath; not in the reference; Gatys et al. 2017, section 4) gives the styles label maps of their own: only the
+style pixels with label k enter region k's style statistics (wct_stylize_guided).  --auto_regions K makes both label maps itself, by k-means
+on the style's features of --auto_level (wct_feature_regions), for ordinary content x style pairs; the files carry _auto=<K>.
 Decoding/encoding files needs Pillow on the host (the reference's own dependency); the GPU library is mandatory: there
 is no CPU fallback.
 """
@@ -116,6 +119,15 @@ def build_parser() -> argparse.ArgumentParser:
                         "between the two feature Gaussians (same target statistics, moves the content least), adain = per-channel "
                         "mean / std matching")
     # not in the reference: patch-based style swap at one cascade level (include/wct_hip_swap.h)
+    p.add_argument("--styleMaskPath", type=str, default=None,
+                   help="with --maskPath / --region_styles: folder of STYLE label maps, style image X.* uses DIR/X.png (same rules as "
+                        "--maskPath, at the style's size after --style_size); only the style pixels with label k enter region k's style "
+                        "statistics; a style without a file is used whole")
+    p.add_argument("--auto_regions", type=int, default=None,
+                   help="K = 2..8: cluster the style's features into K regions (k-means at --auto_level), give every content feature pixel "
+                        "the nearest cluster, and transfer region to region (wct_feature_regions + wct_stylize_guided)")
+    p.add_argument("--auto_level", type=int, default=None, choices=[2, 3, 4, 5], help="with --auto_regions: the level whose features are clustered (default 4)")
+    p.add_argument("--auto_iters", type=int, default=None, help="with --auto_regions: Lloyd iterations, 1..64 (default 10)")
     p.add_argument("--swap_level", type=int, default=None, choices=[2, 3, 4, 5],
                    help="run this level of the cascade as a patch swap (style decorator): every 3x3 content feature patch is replaced by "
                         "its best-matching style patch; the other levels keep --transform (default: off)")
@@ -179,6 +191,9 @@ def out_name(args, imname: str) -> str:
     scale = getattr(args, "level_scale", None)
     if scale:
         tmark += "_scale=%s" % "-".join(t.strip() for t in scale.split(","))                    # in the same place (the two do not mix)
+    auto = getattr(args, "auto_regions", None)
+    if auto:
+        tmark += "_auto=%d" % auto                                                              # in the same place (mixes with neither)
     marks = ("_color=%s" % color if color else "") + ("_smooth=%d" % radius if radius else "")   # runs with and without the flags never collide
     return os.path.join(args.outf, "%s_mode=%s_alpha=%s%s%s_%s" % (args.log_mark, args.mode, args.alpha, tmark, marks, imname))
 
@@ -239,6 +254,15 @@ def load_mask(path: str, shape: Tuple[int, int]):
     return lab
 
 
+def style_mask_path(mask_dir: Optional[str], style_path: str) -> Optional[str]:
+    """--styleMaskPath: style image X.* uses DIR/X.png (X = text before the first dot of the file name); None when there is no such
+    file -- that style is used whole."""
+    if not mask_dir:
+        return None
+    m = os.path.join(mask_dir, os.path.basename(style_path).split(".")[0] + ".png")
+    return m if os.path.isfile(m) else None
+
+
 def region_out_name(args, content_file: str) -> str:
     """<log_mark>_mode=<m>_alpha=<a>_<X>+regions.jpg (out_name with the style stem replaced by 'regions')."""
     return out_name(args, content_file.split(".")[0] + "+regions.jpg")
@@ -251,6 +275,16 @@ def run_regions(args, wct, content_dir, logprinter) -> float:
     jobs = region_jobs(content_dir, args.maskPath, args.picked_content_mark)
     styles = [p for p in args.region_styles.split(",") if p]
     s_dev = [_to_tensor(wct, torch.from_numpy(load_rgb_u8(p)).cuda(), args.style_size) for p in styles]
+    # --styleMaskPath: the styles' own label maps, at each style's size after --style_size (wct_stylize_guided); none -> wct_stylize_regions
+    smask = [style_mask_path(getattr(args, "styleMaskPath", None), p) for p in styles]
+    s_lab = [torch.from_numpy(load_mask(m, (int(t.shape[-2]), int(t.shape[-1])))).cuda() if m else None for m, t in zip(smask, s_dev)]
+    guided = any(m is not None for m in s_lab)
+
+    def stylise(c_f32, st, lab):
+        if guided:
+            return wct.stylize_guided(c_f32, st, lab, s_lab, None, args.alpha, args.num_run)
+        return wct.stylize_regions(c_f32, st, lab, args.alpha, args.num_run)
+
     avg = 0.0
     for i, (cfile, mpath) in enumerate(jobs):
         logprinter("\n" + "*" * 30 + ' #%s: Transferring "%s" by regions (%s)' % (i, cfile, mpath))
@@ -259,12 +293,12 @@ def run_regions(args, wct, content_dir, logprinter) -> float:
         lab = torch.from_numpy(load_mask(mpath, (H, W))).cuda()
         t0 = time.time()
         c_f32 = _to_tensor(wct, c_u8, args.content_size)
-        res = wct.stylize_regions(c_f32, s_dev, lab, args.alpha, args.num_run)
+        res = stylise(c_f32, s_dev, lab)
         if wct.saturation_count(reset=True):
             logprinter("WARNING: f16x3 range exceeded for this content -> recomputing it with exact-fp32 convolutions")
             wct.set_conv_mode("fp32")
             s32 = [_to_tensor(wct, torch.from_numpy(load_rgb_u8(p)).cuda(), args.style_size) for p in styles]
-            res = wct.stylize_regions(c_f32, s32, lab, args.alpha, args.num_run)
+            res = stylise(c_f32, s32, lab)
             wct.sync()
             wct.set_conv_mode("f16x3")
         out = _finish_u8(wct, args, res, c_f32).cpu().numpy()
@@ -282,6 +316,71 @@ def check_region_args(args) -> None:
         n = len([p for p in args.region_styles.split(",") if p])
         if not 1 <= n <= 8:
             raise ValueError("--region_styles: 1 to 8 style images, got %d" % n)
+    if getattr(args, "styleMaskPath", None) is not None:
+        if args.maskPath is None:
+            raise ValueError("--styleMaskPath does nothing without --maskPath / --region_styles")
+        if not os.path.isdir(args.styleMaskPath):
+            raise ValueError("--styleMaskPath %s is not a folder" % args.styleMaskPath)
+
+
+def check_auto_args(args) -> None:
+    """--auto_regions K / --auto_level / --auto_iters: ordinary content x style pairs through the plain wct cascade, region to region."""
+    K, level, iters = getattr(args, "auto_regions", None), getattr(args, "auto_level", None), getattr(args, "auto_iters", None)
+    if K is None:
+        for v, name in ((level, "--auto_level"), (iters, "--auto_iters")):
+            if v is not None:
+                raise ValueError("%s does nothing without --auto_regions" % name)
+        return
+    if not 2 <= K <= 8:
+        raise ValueError("--auto_regions: K = 2..8 expected, got %r" % (K,))
+    if iters is not None and not 1 <= iters <= 64:
+        raise ValueError("--auto_iters: 1..64 expected, got %r" % (iters,))
+    transform = getattr(args, "transform", None) or "wct"
+    clash = [name for flag, name in ((args.maskPath is not None, "--maskPath"), (args.interp_styles is not None, "--interp_styles"),
+                                     (args.weightPath is not None, "--weightPath"), (args.synthesis, "--synthesis"),
+                                     (getattr(args, "swap_level", None), "--swap_level"), (getattr(args, "level_scale", None), "--level_scale"),
+                                     (transform != "wct", "--transform %s" % transform)) if flag]
+    if clash:
+        raise ValueError("--auto_regions does not mix with %s" % ", ".join(clash))
+    if getattr(args, "preserve_color", None) in ("match", "match+luma"):
+        raise ValueError("--auto_regions does not mix with --preserve_color match (it is for one whole style per content); luma goes with it")
+    args.auto_level = 4 if level is None else level
+    args.auto_iters = 10 if iters is None else iters
+
+
+def run_auto(args, wct, pairs, content_dir, style_dir, logprinter) -> float:
+    """--auto_regions: per pair, k-means label maps from the features of --auto_level (wct_feature_regions), then the region-to-region
+    cascade against the one style (wct_stylize_guided); one pair at a time; returns the summed per-pair time."""
+    import torch
+    from PIL import Image
+    K = args.auto_regions
+    avg = 0.0
+    for i, (cfile, sfile) in enumerate(pairs):
+        imname = pair_name(cfile, sfile)
+        logprinter("\n" + "*" * 30 + ' #%s: Transferring "%s" (%d feature regions of level %d, %d iterations)' % (i, imname, K, args.auto_level, args.auto_iters))
+        c_u8 = torch.from_numpy(load_rgb_u8(os.path.join(content_dir, cfile))).pin_memory().cuda(non_blocking=True)
+        s_u8 = torch.from_numpy(load_rgb_u8(os.path.join(style_dir, sfile))).pin_memory().cuda(non_blocking=True)
+        t0 = time.time()
+        c_f32 = _to_tensor(wct, c_u8, args.content_size)
+
+        def once():
+            s_f32 = _to_tensor(wct, s_u8, args.style_size)
+            lab_c, lab_s = wct.feature_regions(c_f32, s_f32, K, args.auto_level, args.auto_iters)
+            return wct.stylize_guided(c_f32, [s_f32], lab_c, [lab_s], [0] * K, args.alpha, args.num_run)
+
+        res = once()
+        if wct.saturation_count(reset=True):
+            logprinter("WARNING: f16x3 range exceeded for this pair -> recomputing it with exact-fp32 convolutions")
+            wct.set_conv_mode("fp32")
+            res = once()
+            wct.sync()
+            wct.set_conv_mode("f16x3")
+        out = _finish_u8(wct, args, res, c_f32).cpu().numpy()
+        Image.fromarray(out).save(out_name(args, imname))
+        dt = time.time() - t0
+        avg += dt
+        logprinter("Elapsed time is: %.4f seconds" % dt)
+    return avg
 
 
 def check_color_args(args) -> None:
@@ -988,6 +1087,7 @@ def main(argv: Optional[List[str]] = None) -> int:
     check_transform_args(args)
     check_swap_args(args)
     check_scale_args(args)
+    check_auto_args(args)
     os.makedirs(args.outf, exist_ok=True)
     logprinter = LogPrinter(args.debug, os.path.join(args.outf, "log_%s_%s.txt" % (args.log_mark, args.mode)))
     logprinter(sorted(vars(args).items()))
@@ -1038,6 +1138,13 @@ def main(argv: Optional[List[str]] = None) -> int:
         if args.pipeline > 0:
             logprinter("--pipeline is ignored with --level_scale: scale-controlled runs use the serial loop")
         avg = run_scale(args, wct, pairs, content_dir, style_dir, logprinter)
+        if pairs:
+            logprinter("Processed %d images. Average processing time per pair is: %.4f seconds" % (len(pairs), avg / len(pairs)))
+        return 0
+    if args.auto_regions:
+        if args.pipeline > 0:
+            logprinter("--pipeline is ignored with --auto_regions: feature-region runs use the serial loop")
+        avg = run_auto(args, wct, pairs, content_dir, style_dir, logprinter)
         if pairs:
             logprinter("Processed %d images. Average processing time per pair is: %.4f seconds" % (len(pairs), avg / len(pairs)))
         return 0

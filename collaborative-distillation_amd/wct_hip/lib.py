@@ -63,6 +63,14 @@ SCALE_MAX_DIVISOR = 16                                              # WCT_SCALE_
 SCALE_MAX_SHRINK = 32                                               # WCT_SCALE_MAX_SHRINK
 SCALE_DETAIL = 1.0                                                  # WCT_SCALE_DETAIL
 
+# every symbol include/wct_hip_guided.h declares (region-to-region transfer: style label maps, k-means feature regions); bound from the same libwct_hip.so
+SYMBOLS_GUIDED = ["wct_stylize_guided", "wct_kmeans_assign", "wct_kmeans_seed", "wct_feature_regions"]
+GUIDED_MAX_REGIONS = 8                                              # WCT_GUIDED_MAX_REGIONS
+GUIDED_MAX_STYLES = 8                                               # WCT_GUIDED_MAX_STYLES
+KMEANS_MAX_K = 8                                                    # WCT_KMEANS_MAX_K
+KMEANS_MAX_ITERS = 64                                               # WCT_KMEANS_MAX_ITERS
+KMEANS_DEAD_VARIANCE = 1e-12                                        # WCT_KMEANS_DEAD_VARIANCE
+
 
 class WctLayer(ctypes.Structure):
     _fields_ = [("cin", c_int), ("cout", c_int), ("pool_after", c_int), ("up_after", c_int),
@@ -199,6 +207,10 @@ def load() -> ctypes.CDLL:
     lib.wct_resample_planar.argtypes = [c_void_p, vp, c_int, c_int, vp, c_int, c_int, c_int]
     lib.wct_pyramid_merge.argtypes = [c_void_p, vp, vp, c_int, c_int, vp, c_int, c_int, c_float, vp]
     lib.wct_stylize_scaled.argtypes = [c_void_p, vp, c_int, c_int, vp, c_int, c_int, c_float, c_int, ip, c_float, vp, ip, ip]
+    lib.wct_stylize_guided.argtypes = [c_void_p, vp, c_int, c_int, vp, c_int, c_int, POINTER(c_void_p), ip, ip, POINTER(c_void_p), ip, fp, c_int, vp, ip, ip]
+    lib.wct_kmeans_assign.argtypes = [c_void_p, vp, c_int, c_int, c_int, vp, vp, vp, c_int, vp, vp, vp, vp, vp]
+    lib.wct_kmeans_seed.argtypes = [c_void_p, vp, c_int, c_int, c_int, vp, vp, c_int, vp, vp]
+    lib.wct_feature_regions.argtypes = [c_void_p, c_int, vp, c_int, c_int, vp, c_int, c_int, c_int, c_int, vp, vp, vp]
     lib.wct_set_transform.argtypes = [c_void_p, c_int]
     lib.wct_get_transform.argtypes = [c_void_p, ip]
     lib.wct_transform_solve.argtypes = [c_void_p, c_int, c_int, c_double, vp, vp, vp, c_double, vp, vp, ip]

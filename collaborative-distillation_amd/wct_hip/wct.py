@@ -1179,6 +1179,103 @@ class WCT:
                                                 out.data_ptr(), byref(ho), byref(wo)))
         return out.view(-1)[: 3 * ho.value * wo.value].view(1, 3, ho.value, wo.value)
 
+    # ------------------------------------------------------------------ region-to-region transfer (include/wct_hip_guided.h)
+    @torch.no_grad()
+    def stylize_guided(self, contentImg: torch.Tensor, styles, labels: torch.Tensor, style_labels=None, region_style=None, alpha=None,
+                       num_run: int = 1, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The cascade with content regions AND style regions: `labels` (uint8 H x W, CUDA) as in stylize_regions; `style_labels` one
+        uint8 map (or None = the whole image) per style, at the style's size: only the style pixels with label k enter region k's style
+        statistics; `region_style[k]` names the style of region k (default: one region per style, region k against style k);
+        `alpha` is one float or one per region."""
+        c = self._img(contentImg)
+        H, W = int(c.shape[1]), int(c.shape[2])
+        ss = [self._img(s) for s in styles]
+        S = len(ss)
+        maps = [None] * S if style_labels is None else list(style_labels)
+        if len(maps) != S:
+            raise ValueError("style_labels: expected %d entries (one per style, None = unmapped), got %d" % (S, len(maps)))
+        if not labels.is_cuda:
+            raise ValueError("labels must be a CUDA uint8 tensor")
+        lab = self._labels(labels, H, W)
+        for i, m in enumerate(maps):
+            if m is not None:
+                if not m.is_cuda:
+                    raise ValueError("style_labels[%d] must be a CUDA uint8 tensor" % i)
+                maps[i] = self._labels(m, int(ss[i].shape[1]), int(ss[i].shape[2]))
+        if region_style is None:
+            K, rs = S, list(range(S))
+        else:
+            rs = [int(v) for v in region_style]
+            K = len(rs)
+        if alpha is None:
+            alpha = self.alpha
+        al = [float(alpha)] * K if isinstance(alpha, (int, float)) else [float(a) for a in alpha]
+        if len(al) != K:
+            raise ValueError("alpha: expected 1 or %d values, got %d" % (K, len(al)))
+        out = self._out_image(out, H, W)
+        ptrs = (c_void_p * max(S, 1))(*[s.data_ptr() for s in ss])
+        mptrs = (c_void_p * max(S, 1))(*[(m.data_ptr() if m is not None else None) for m in maps])
+        hs = (c_int * max(S, 1))(*[int(s.shape[1]) for s in ss])
+        ws = (c_int * max(S, 1))(*[int(s.shape[2]) for s in ss])
+        rv = (c_int * max(K, 1))(*rs)
+        av = (ctypes.c_float * max(K, 1))(*al)
+        ho, wo = c_int(), c_int()
+        self._stream()
+        self._chk(self._lib.wct_stylize_guided(self._ctx, c.data_ptr(), H, W, lab.data_ptr(), K, S, ptrs, hs, ws, mptrs, rv, av, int(num_run),
+                                               out.data_ptr(), byref(ho), byref(wo)))
+        self._guided_keep = (ss, maps)      # the side stream reads them asynchronously
+        return out.view(-1)[: 3 * ho.value * wo.value].view(1, 3, ho.value, wo.value)
+
+    def _kmeans_args(self, feat_nhwc, shift, scale):
+        f = self._nhwc(feat_nhwc)
+        h, w, C = (int(v) for v in f.shape)
+        return f, h, w, C, self._dev_f64(shift, C, "shift"), self._dev_f64(scale, C, "scale")
+
+    @torch.no_grad()
+    def kmeans_assign(self, feat_nhwc: torch.Tensor, shift: torch.Tensor, scale: torch.Tensor, centroids: torch.Tensor, want_labels: bool = True,
+                      want_next: bool = True):
+        """One Lloyd step on an NHWC feature [1,h,w,C] in the standardised space z = (x - shift) * scale against `centroids` [K,C] (fp64):
+        (labels uint8 [h,w] or None, n [K], sum [K,C], cost [1], next [K,C] or None), all on the device, nothing read back."""
+        f, h, w, C, sh, sc = self._kmeans_args(feat_nhwc, shift, scale)
+        K = int(centroids.numel()) // C
+        cen = self._dev_f64(centroids, K * C, "centroids")
+        dev = f.device
+        lab = torch.empty((h, w), device=dev, dtype=torch.uint8) if want_labels else None
+        n = torch.empty(K, device=dev, dtype=torch.float64)
+        s = torch.empty((K, C), device=dev, dtype=torch.float64)
+        cost = torch.empty(1, device=dev, dtype=torch.float64)
+        nxt = torch.empty((K, C), device=dev, dtype=torch.float64) if want_next else None
+        self._stream()
+        self._chk(self._lib.wct_kmeans_assign(self._ctx, f.data_ptr(), C, h, w, sh.data_ptr(), sc.data_ptr(), cen.data_ptr(), K,
+                                              lab.data_ptr() if want_labels else None, n.data_ptr(), s.data_ptr(), cost.data_ptr(),
+                                              nxt.data_ptr() if want_next else None))
+        return lab, n, s, cost, nxt
+
+    @torch.no_grad()
+    def kmeans_seed(self, feat_nhwc: torch.Tensor, shift: torch.Tensor, scale: torch.Tensor, K: int):
+        """The deterministic farthest-first start: (centroids [K,C] fp64, idx [K] int32 pixel indices)."""
+        f, h, w, C, sh, sc = self._kmeans_args(feat_nhwc, shift, scale)
+        cen = torch.empty((int(K), C), device=f.device, dtype=torch.float64)
+        idx = torch.empty(int(K), device=f.device, dtype=torch.int32)
+        self._stream()
+        self._chk(self._lib.wct_kmeans_seed(self._ctx, f.data_ptr(), C, h, w, sh.data_ptr(), sc.data_ptr(), int(K), cen.data_ptr(), idx.data_ptr()))
+        return cen, idx
+
+    @torch.no_grad()
+    def feature_regions(self, contentImg: torch.Tensor, styleImg: torch.Tensor, K: int, level: int = 4, iters: int = 10, want_centroids: bool = False):
+        """Label maps from k-means on the level's features: K clusters of the STYLE's standardised features, every content feature pixel
+        given the nearest one: (labels_c uint8 [H,W], labels_s uint8 [Hs,Ws][, centroids [K,C]]) for
+        stylize_guided(content, [style], labels_c, [labels_s], region_style=[0] * K)."""
+        c, s = self._img(contentImg), self._img(styleImg)
+        H, W, Hs, Ws = int(c.shape[1]), int(c.shape[2]), int(s.shape[1]), int(s.shape[2])
+        lc = torch.empty((H, W), device=c.device, dtype=torch.uint8)
+        ls = torch.empty((Hs, Ws), device=c.device, dtype=torch.uint8)
+        cen = torch.empty((int(K), self._feature_channels(int(level)) if 1 <= int(level) <= 5 else 1), device=c.device, dtype=torch.float64) if want_centroids else None
+        self._stream()
+        self._chk(self._lib.wct_feature_regions(self._ctx, int(level), c.data_ptr(), H, W, s.data_ptr(), Hs, Ws, int(K), int(iters), lc.data_ptr(),
+                                                ls.data_ptr(), cen.data_ptr() if want_centroids else None))
+        return (lc, ls, cen) if want_centroids else (lc, ls)
+
     # ------------------------------------------------------------------ style interpolation and per-pixel style weights
     def _styles(self, styles):
         ss = [self._img(s) for s in styles]
