@@ -1,9 +1,40 @@
 // The column-sharded cascade behind the C ABI (include/wct_hip.h wct_stylize_sharded, wct_shard_geometry, wct_style_moments,
-// wct_style_solve, wct_comm_attach_collectives).  NOT a stand-alone header: wct_api.hip includes it once, after its internal helpers
-// (encode_impl, moments_impl, eig_impl, ...) and the split-level entry points -- one translation unit, no second copy of wct_ctx.
+// wct_style_solve, wct_comm_*, wct_level_sharded) and its transports: RCCL resolved at run time, or the caller's wct_collectives table.
 //
 // What runs here is WCT.py:120-125 (levels 5 -> 1 of styleTransfer, WCT.py:98-106) on ONE rank's column strip; the geometry is the one
 // wct_hip/sharded.py documents (and still implements over torch.distributed, as the checker of this path: bit-identical results).
+#include "wct_ctx.h"
+
+#include <dlfcn.h>
+#include <mutex>
+
+using namespace wct_host;
+
+// RCCL, resolved at run time (wct_comm_load): the library keeps no link-time dependency on it
+struct NcclUid { char b[128]; };      // nccl.h ncclUniqueId: 128 opaque bytes, passed BY VALUE to ncclCommInitRank
+struct RcclApi {
+  void* lib = nullptr;
+  int (*GetUniqueId)(void*) = nullptr;
+  int (*CommInitRank)(void**, int, NcclUid, int) = nullptr;
+  int (*CommDestroy)(void*) = nullptr;
+  int (*AllReduce)(const void*, void*, size_t, int, int, void*, hipStream_t) = nullptr;
+  int (*Broadcast)(const void*, void*, size_t, int, int, void*, hipStream_t) = nullptr;   // (send, recv, count, datatype, root, comm, stream)
+  int (*Send)(const void*, size_t, int, int, void*, hipStream_t) = nullptr;               // (buf, count, datatype, peer, comm, stream)
+  int (*Recv)(void*, size_t, int, int, void*, hipStream_t) = nullptr;
+  int (*GroupStart)() = nullptr;
+  int (*GroupEnd)() = nullptr;
+  const char* (*GetErrorString)(int) = nullptr;
+  std::string path;
+};
+static RcclApi g_rccl;
+static std::mutex g_rccl_mutex;                  // wct_comm_load may be called from several contexts' threads
+constexpr int NCCL_FLOAT64 = 8, NCCL_INT8 = 0, NCCL_SUM = 0;    // nccl.h: ncclDataType_t ncclFloat64 = 8, ncclInt8 = ncclChar = 0; ncclRedOp_t ncclSum = 0
+
+namespace wct_host {
+void release_comm(wct_ctx* ctx) {
+  if (ctx->comm && ctx->comm_owned && g_rccl.CommDestroy) (void)g_rccl.CommDestroy(ctx->comm);
+}
+}  // namespace wct_host
 
 namespace shard {
 namespace {
@@ -474,6 +505,135 @@ int wct_stylize_sharded(wct_ctx* ctx, const float* content_ext, int H, int W_tot
   if (Wo_out) *Wo_out = Wo;
   ctx->quiet_readback = false;
   return range_readback(ctx);
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------------------
+// RCCL inside the boundary ("multi-GPU variant takes an ncclComm_t").  One level of a column-sharded cascade is ONE call:
+// encoder + raw moments over the owned feature columns -> ncclAllReduce(SUM, fp64) of [sum | sumsq | range flag] on the context's
+// stream -> matrix functions against the level's (imported) style statistics -> fold -> decoder.  RCCL's entry points are looked up
+// at run time in the librccl the host process names (wct_comm_load; the Python mirror passes the one torch has loaded), so the
+// library links against nothing new and single-GPU users never touch RCCL.
+namespace {
+int rccl_ready(wct_ctx* ctx) {
+  if (g_rccl.AllReduce) return WCT_OK;
+  return fail(ctx, WCT_ERR_STATE, "RCCL is not loaded: call wct_comm_load(path of librccl.so) first");
+}
+}  // namespace
+
+extern "C" {
+
+int wct_comm_load(const char* path) {
+  std::lock_guard<std::mutex> lock(g_rccl_mutex);
+  if (g_rccl.AllReduce) return WCT_OK;
+  // an explicit path is THE library the host process uses (torch's bundled librccl.so): if it cannot be opened, fail -- mapping a second,
+  // different RCCL into the process silently is worse than an error.  Without a path: the loader's search path, then /opt/rocm.
+  const char* search[] = {"librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so"};
+  void* h = nullptr;
+  if (path && *path) {
+    h = dlopen(path, RTLD_NOW | RTLD_LOCAL);      // a library the process has already mapped is reused, not loaded twice
+    if (h) g_rccl.path = path;
+  } else {
+    for (const char* c : search) {
+      h = dlopen(c, RTLD_NOW | RTLD_LOCAL);
+      if (h) { g_rccl.path = c; break; }
+    }
+  }
+  if (!h) return WCT_ERR_STATE;
+  RcclApi api;
+  api.lib = h;
+  api.path = g_rccl.path;
+  api.GetUniqueId = reinterpret_cast<decltype(api.GetUniqueId)>(dlsym(h, "ncclGetUniqueId"));
+  api.CommInitRank = reinterpret_cast<decltype(api.CommInitRank)>(dlsym(h, "ncclCommInitRank"));
+  api.CommDestroy = reinterpret_cast<decltype(api.CommDestroy)>(dlsym(h, "ncclCommDestroy"));
+  api.GetErrorString = reinterpret_cast<decltype(api.GetErrorString)>(dlsym(h, "ncclGetErrorString"));
+  api.AllReduce = reinterpret_cast<decltype(api.AllReduce)>(dlsym(h, "ncclAllReduce"));
+  api.Broadcast = reinterpret_cast<decltype(api.Broadcast)>(dlsym(h, "ncclBroadcast"));
+  api.Send = reinterpret_cast<decltype(api.Send)>(dlsym(h, "ncclSend"));
+  api.Recv = reinterpret_cast<decltype(api.Recv)>(dlsym(h, "ncclRecv"));
+  api.GroupStart = reinterpret_cast<decltype(api.GroupStart)>(dlsym(h, "ncclGroupStart"));
+  api.GroupEnd = reinterpret_cast<decltype(api.GroupEnd)>(dlsym(h, "ncclGroupEnd"));
+  if (!api.GetUniqueId || !api.CommInitRank || !api.CommDestroy || !api.AllReduce || !api.Broadcast || !api.Send || !api.Recv || !api.GroupStart || !api.GroupEnd) {
+    g_rccl.path.clear();
+    return WCT_ERR_STATE;
+  }
+  g_rccl = api;
+  return WCT_OK;
+}
+
+const char* wct_comm_library(void) { return g_rccl.AllReduce ? g_rccl.path.c_str() : ""; }
+
+int wct_comm_unique_id(unsigned char* id128) {
+  if (!g_rccl.AllReduce || !id128) return WCT_ERR_STATE;
+  return g_rccl.GetUniqueId(id128) == 0 ? WCT_OK : WCT_ERR_HIP;
+}
+
+int wct_comm_init(wct_ctx* ctx, int nranks, int rank, const unsigned char* id128) {
+  if (!ctx) return WCT_ERR_INVALID;
+  WCT_GUARD(ctx);
+  if (int rc = rccl_ready(ctx)) return rc;
+  if (!id128 || nranks < 1 || rank < 0 || rank >= nranks) return fail(ctx, WCT_ERR_INVALID, "comm_init: bad arguments (nranks %d, rank %d)", nranks, rank);
+  if (ctx->comm || ctx->coll_set) return fail(ctx, WCT_ERR_STATE, "comm_init: the context already has a communicator");
+  NcclUid uid;
+  memcpy(uid.b, id128, 128);
+  void* comm = nullptr;
+  const int r = g_rccl.CommInitRank(&comm, nranks, uid, rank);     // collective over the job's ranks; the context's device is current
+  if (r != 0 || !comm) return fail(ctx, WCT_ERR_HIP, "ncclCommInitRank(%d ranks, rank %d): %s", nranks, rank, g_rccl.GetErrorString ? g_rccl.GetErrorString(r) : "error");
+  ctx->comm = comm; ctx->comm_owned = true; ctx->comm_ranks = nranks; ctx->comm_rank = rank;
+  shard::install_rccl(ctx);
+  ctx->coll_set = true;
+  return WCT_OK;
+}
+
+int wct_comm_attach(wct_ctx* ctx, void* nccl_comm, int nranks, int rank) {
+  if (!ctx) return WCT_ERR_INVALID;
+  WCT_GUARD(ctx);
+  if (int rc = rccl_ready(ctx)) return rc;
+  if (!nccl_comm || nranks < 1 || rank < 0 || rank >= nranks) return fail(ctx, WCT_ERR_INVALID, "comm_attach: bad arguments");
+  if (ctx->comm || ctx->coll_set) return fail(ctx, WCT_ERR_STATE, "comm_attach: the context already has a communicator");
+  ctx->comm = nccl_comm; ctx->comm_owned = false; ctx->comm_ranks = nranks; ctx->comm_rank = rank;
+  shard::install_rccl(ctx);
+  ctx->coll_set = true;
+  return WCT_OK;
+}
+
+int wct_comm_destroy(wct_ctx* ctx) {
+  if (!ctx) return WCT_ERR_INVALID;
+  WCT_GUARD(ctx);
+  if (ctx->comm && ctx->comm_owned && g_rccl.CommDestroy) {
+    (void)hipStreamSynchronize(ctx->main.stream);
+    (void)g_rccl.CommDestroy(ctx->comm);
+  }
+  ctx->comm = nullptr; ctx->comm_owned = false; ctx->comm_ranks = 0; ctx->comm_rank = 0;
+  ctx->coll = wct_collectives{}; ctx->coll_set = false; ctx->coll_rccl = false; ctx->shard_emulate = false;
+  return WCT_OK;
+}
+
+int wct_level_sharded(wct_ctx* ctx, int level, const float* content, int H, int W, int x0, int x1, double n_total, float alpha,
+                      float* out, int* Ho, int* Wo, double* range_total) {
+  if (!ctx) return WCT_ERR_INVALID;
+  WCT_GUARD(ctx);
+  if (!ctx->coll_set) return fail(ctx, WCT_ERR_STATE, "level_sharded: no communicator (wct_comm_init / wct_comm_attach / wct_comm_attach_collectives)");
+  if (!valid_level(level) || !content || !out || !(n_total >= 1.0)) return fail(ctx, WCT_ERR_INVALID, "level_sharded: bad arguments");
+  Module& me = ctx->mod[WCT_KIND_ENC][level];
+  if (!me.loaded) return fail(ctx, WCT_ERR_STATE, "encoder %d not loaded", level);
+  if (!ctx->eigS[level].p) return fail(ctx, WCT_ERR_STATE, "level_sharded: no style statistics for level %d (wct_style_prepare / wct_style_import)", level);
+  const int C = me.layers.back().d.cout;
+  const size_t npk = (size_t)C * C + C + 1;
+  if (int rc = ensure(ctx, ctx->packed, npk * sizeof(double))) return rc;
+  double* pk = reinterpret_cast<double*>(ctx->packed.p);
+  // the four steps below are wct_content_encode / wct_range_flag_f64 / [all-reduce] / wct_content_solve / wct_content_decode in this order,
+  // on the same buffers' worth of arithmetic: results are those of the split-level path bit for bit (tests/test_sharded_gpu.py)
+  int h = 0, w = 0;
+  if (int rc = wct_content_encode(ctx, level, content, H, W, x0, x1, pk, pk + C, &h, &w)) return rc;
+  HIPCHK(ctx, launch_counter_to_f64(ctx->sat_dev, pk + C + (size_t)C * C, ctx->main.stream));
+  COLLCHK(ctx, "all-reduce (content moments)", ctx->coll.all_reduce_sum_f64(ctx->coll.user, pk, npk, ctx->main.stream));
+  if (range_total) HIPCHK(ctx, hipMemcpyAsync(range_total, pk + C + (size_t)C * C, sizeof(double), hipMemcpyDeviceToDevice, ctx->main.stream));
+  double *M, *b;
+  if (int rc = mb_view(ctx, &M, &b)) return rc;
+  if (int rc = wct_content_solve(ctx, level, n_total, pk, pk + C, alpha, M, b)) return rc;
+  return wct_content_decode(ctx, level, M, b, out, Ho, Wo);
 }
 
 }  // extern "C"

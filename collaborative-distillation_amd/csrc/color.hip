@@ -273,7 +273,7 @@ long color_moments_max_pixels() { return (long)CM_TILE * CM_THREADS * 4096; }
 size_t color_moments_workspace_bytes(long npix) { return (size_t)color_moments_tiles(npix) * 9 * sizeof(double); }
 
 hipError_t launch_color_moments(const float* planar, long npix, double* sum, double* sumsq, void* workspace, size_t workspace_bytes, hipStream_t s) {
-  // arguments are checked where they can be answered with a message (wct_api.hip); this one guards the partials' bounds
+  // arguments are checked where they can be answered with a message (api_image.hip); this one guards the partials' bounds
   if (workspace_bytes < color_moments_workspace_bytes(npix)) return hipErrorInvalidValue;
   const long ntiles = color_moments_tiles(npix);
   double* partial = reinterpret_cast<double*>(workspace);

@@ -992,7 +992,7 @@ __global__ __launch_bounds__(32 * TH, TH == 8 ? 2 : 1) void dec_tail_kernel(Tail
 
 // ---- the same tail with conv12 evaluated on the LOW-RESOLUTION input (up_in = 1 only).
 // conv12 runs behind the nearest-x2 upsample, so each output parity (a, b) is a 2x2 convolution of the low-resolution map with summed
-// taps (wct_api.hip pack_up_phase_f16): K = 2 x 2 x 16 = 64 = two 16x16x32 K-steps (tap row i; kq -> column j = kq >> 1, channels
+// taps (api_model.hip pack_up_phase_f16): K = 2 x 2 x 16 = 64 = two 16x16x32 K-steps (tap row i; kq -> column j = kq >> 1, channels
 // 8 (kq & 1) ..) = 6 MFMAs and 4 operand reads per 16 halo pixels instead of 15 and 10, and the staged window is the 18 x (TH / 2 + 2)
 // low-resolution pixels the tile touches instead of their 36 x (TH + 4) fourfold copies (16 KB instead of 64.5 KB at TH = 24).
 // A 16-pixel group must share its parity: the 34 x (TH + 2) halo is cut into row groups g = 2 row + c (pixels x = 2 li + 1 - c: every

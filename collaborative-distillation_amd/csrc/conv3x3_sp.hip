@@ -505,7 +505,7 @@ __global__ __launch_bounds__(512) void conv3x3_sp3_kernel(SpArgs a) {
 // =====================================================================================================================
 // Layers BEHIND a nearest-x2 upsample (CONV_UP_IN), on the low-resolution grid.
 // The 3x3 convolution of the upsampled map is, per output parity (a, b), a 2x2 convolution of the low-resolution map with
-// summed taps (wct_api.hip pack_up_phase_f16): 4 instead of 9 products per output and channel pair.  The kernel above gathered
+// summed taps (api_model.hip pack_up_phase_f16): 4 instead of 9 products per output and channel pair.  The kernel above gathered
 // the upsampled 34 x 18 halo (each low-resolution pixel up to four times) and ran nine taps; this one stages the LOW-RESOLUTION
 // 34 x 18 halo of a 32 x 16 low-resolution tile (= 64 x 32 outputs) and a work unit is (tile, 32-cout group, row parity a): its
 // two accumulator sets are the column parities b = 0, 1 (the register budget of the 64-cout kernel above), its job walks the six

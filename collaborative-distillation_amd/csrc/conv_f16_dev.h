@@ -500,7 +500,7 @@ __device__ __forceinline__ void c3_block_store(const f32x4 (&acc)[4], float inv,
 // apart, two half-empty K-steps each: six MFMAs).  Lane group kq of K-step s holds the singles l1_single(s, kq, 0 / 1)
 // (wct_common.h: ordered so that the reads are free of bank conflicts): two 8-byte LDS reads at per-lane offsets (window position,
 // hi or lo plane), fixed for the kernel's lifetime.
-// Weights: [cout tile][s][kq][16 couts] x 8 halfs (wct_api.hip pack_head_f16).
+// Weights: [cout tile][s][kq][16 couts] x 8 halfs (api_model.hip pack_head_f16).
 struct L1Conv { const u32x4* w; const float* b; float inv; };
 struct L1Weights { f16x8 a[2][4]; int off[4][2]; f32x4 bias[2]; float inv; };
 

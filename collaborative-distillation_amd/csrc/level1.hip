@@ -328,7 +328,7 @@ __global__ __launch_bounds__(256, 2) void in3_wide_f32_kernel(In3WideArgs a) {
   for (int e = tid; e < IMGF_PLANE + 4; e += 256) imgF[3 * IMGF_PLANE + e] = 0.f;   // the "0" slot of RGB0 (zero weights, finite data)
   float wa[4][9];
   f32x4 bias[4];
-  const float* wf = reinterpret_cast<const float*>(a.w);     // [tap][k = 4][64] fp32 (wct_api.hip pack_weights, in3)
+  const float* wf = reinterpret_cast<const float*>(a.w);     // [tap][k = 4][64] fp32 (api_model.hip pack_weights, in3)
 #pragma unroll
   for (int ct = 0; ct < 4; ++ct) {
 #pragma unroll

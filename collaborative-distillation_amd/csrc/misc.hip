@@ -455,7 +455,7 @@ hipError_t launch_counter_to_f64(const unsigned* counter, double* dst, hipStream
   return hipGetLastError();
 }
 
-// ---- pitched block copy (wct_api.hip wct_stylize_sharded: level crops, halo packing and assembly of planar images; 3 planes of H rows
+// ---- pitched block copy (api_sharded.hip wct_stylize_sharded: level crops, halo packing and assembly of planar images; 3 planes of H rows
 //      are 3H rows of one pitch).  One float per thread and grid-stride: the blocks are 2 ... 1600 columns wide, HBM-bound, a few us.
 namespace {
 __global__ __launch_bounds__(256) void copy_block_kernel(const float* __restrict__ src, long src_pitch, float* __restrict__ dst, long dst_pitch,

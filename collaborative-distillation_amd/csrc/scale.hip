@@ -294,7 +294,7 @@ size_t scale_table_bytes(int H, int W, int oH, int oW, int filter) {
 
 hipError_t launch_scale(const float* a, const float* b, const float* c, float gain, int H, int W, float* out, int oH, int oW, int filter, void* tab,
                         size_t tab_bytes, hipStream_t s) {
-  // arguments are checked where they can be answered with a message (wct_api.hip); this one guards what the kernel's bounds rest on
+  // arguments are checked where they can be answered with a message (api_image.hip); this one guards what the kernel's bounds rest on
   if (!a || !out || H < 1 || W < 1 || oH < 1 || oW < 1 || (filter != RESIZE_BILINEAR && filter != RESIZE_BICUBIC) || (b == nullptr) != (c == nullptr) ||
       !tab || tab_bytes < scale_table_bytes(H, W, oH, oW, filter))
     return hipErrorInvalidValue;

@@ -208,7 +208,7 @@ size_t smooth_ab_bytes(long npix) { return (size_t)12 * sizeof(float) * (size_t)
 
 hipError_t launch_guided_filter(const float* src, int Ho, int Wo, const float* guide, int Hg, int Wg, int r, double eps, float* out_planar,
                                 uint8_t* out_hwc, int round_mode, double* sums, size_t sums_bytes, float* ab, size_t ab_bytes, hipStream_t s) {
-  // arguments are checked where they can be answered with a message (wct_api.hip); this one guards the intermediates' bounds
+  // arguments are checked where they can be answered with a message (api_image.hip); this one guards the intermediates' bounds
   const long npix = (long)Ho * Wo;
   if (sums_bytes < smooth_sums_bytes(npix) || ab_bytes < smooth_ab_bytes(npix)) return hipErrorInvalidValue;
   const int vseg = smooth_vseg(r), nseg = (Wo + SM_HSEG - 1) / SM_HSEG;

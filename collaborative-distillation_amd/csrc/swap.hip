@@ -240,7 +240,7 @@ size_t swap_norm_bytes(long nk) { return (size_t)nk * sizeof(float); }
 
 hipError_t launch_patch_match(const float* q, int h, int w, const float* k, int hs, int ws, int C, int key_chunk, int32_t* idx, float* best,
                               void* run, size_t run_bytes, float* rnorm, size_t norm_bytes, unsigned* sat, hipStream_t s) {
-  // arguments are checked where they can be answered with a message (wct_api.hip); this one guards the intermediates' bounds
+  // arguments are checked where they can be answered with a message (api_swap.hip); this one guards the intermediates' bounds
   const int qh = h - 2, qw = w - 2, kh = hs - 2, kw = ws - 2;
   const long nq = (long)qh * qw, nk = (long)kh * kw;
   if (qh < 1 || qw < 1 || kh < 1 || kw < 1 || nk > INT_MAX || key_chunk < 1 || (C & 3) || C < 4) return hipErrorInvalidValue;

@@ -21,7 +21,7 @@ static inline const char* wct_debug_env(const char* name) {
 
 // What a size-selected launcher chose for its last launch on this host thread (launch_enc_head, launch_dec_tail, launch_l1_decode,
 // launch_conv3x3_f16, launch_conv3x3_sp).  The launchers are free functions without a context, so they leave the choice here and
-// wct_api.hip's ProfScope appends it to the profile record's name as "#<form><tile_h>[m]" when wct_debug_set("prof_forms", 1) is on
+// wct_ctx.h's ProfScope appends it to the profile record's name as "#<form><tile_h>[m]" when wct_debug_set("prof_forms", 1) is on
 // (tests/test_geometry_gpu.py).  form: 'r' two-role head, 't' plain nine-tap tiles, 'u' upsample (2x2 per parity) form, 's' small-map
 // form, '3' three-stage persistent kernel; 0 = the launcher has a single form and says nothing.  multi: the grid is smaller than
 // tiles x cout groups, so some workgroup walks more than one unit.
@@ -47,7 +47,7 @@ __device__ __forceinline__ void sat_raise(unsigned* counter) {
 }
 
 // K layout of the 3-channel first conv on 16x16x32 f16 MFMAs (conv_f16_dev.h l1_conv_group, enc_head_kernel; host packing
-// wct_api.hip pack_head_f16): 27 "singles" (split term 0: w_hi x_hi, 1: w_hi x_lo, 2: w_lo x_hi; window position pos = 3 dy + dx;
+// api_model.hip pack_head_f16): 27 "singles" (split term 0: w_hi x_hi, 1: w_hi x_lo, 2: w_lo x_hi; window position pos = 3 dy + dx;
 // 4 halfs RGB0 each) in 4 K-steps x 4 lane groups x 2.  One ds_read_b64 serves 32 lanes = two lane groups: their two singles are
 // always in the SAME window row and the SAME plane (hi or lo), so the two 128-byte runs overlap on identical addresses instead of
 // landing on the same banks 288 bytes apart (the contiguous order 9 term + pos did: 25 LDS cycles per 16 reads instead of 16).

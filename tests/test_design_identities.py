@@ -16,7 +16,7 @@ def _conv3x3_reflect(x, w):
     return out
 
 
-# R(a, i): taps of the 3-tap axis that fall on patch row i for output parity a (wct_api.hip pack_up_phase_f16 / pack_up_sp_f16)
+# R(a, i): taps of the 3-tap axis that fall on patch row i for output parity a (api_model.hip pack_up_phase_f16 / pack_up_sp_f16)
 RUNS = {(0, 0): (0,), (0, 1): (1, 2), (1, 0): (0, 1), (1, 1): (2,)}
 
 

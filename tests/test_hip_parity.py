@@ -628,7 +628,7 @@ def test_mode_16x_kd2sd_uses_16x_graphs(torch_cuda, wct16, weights16x):
 def test_wide_model_deferred_solves_fall_back(torch_cuda, tmp_path):
     """--mode original: the C > 128 matrix functions no longer synchronise the host once per solve; the cascade-type calls enqueue
     everything, synchronise once, look at the iterations' outcomes and repeat the call the synchronous way if one failed
-    (wct_api.hip with_deferred_solves).  Forced here: with an iteration budget of 3 (WCT_NS_MAXIT, honoured under WCT_DEBUG) no
+    (wct_ctx.h with_deferred_solves).  Forced here: with an iteration budget of 3 (WCT_NS_MAXIT, honoured under WCT_DEBUG) no
     deflated iteration can converge, so every call must come back through the synchronous path and its global-memory Jacobi net --
     and agree with the normal run to the solvers' agreement (1e-5 of the output range; level 2, C = 128, takes the deflated path
     in a wide model too).  A fresh process per setting: the budget is read once."""

@@ -1,12 +1,12 @@
 #!/usr/bin/env python3
 """Static audit of this directory against the CURRENT library (VERDICT r3 task 8): every script must byte-compile, and every WCT_*
-environment variable / wct_debug_set key it uses must still exist in csrc/, wct_hip/ or bench.py.  Prints one row per script; exit 1 on a
+environment variable / wct_debug_set key it uses must still exist in csrc/, wct_hip/, build.sh or bench.py.  Prints one row per script; exit 1 on a
 stale reference.  (Run by tests/test_abi_cpu.py::test_experiment_scripts_reference_live_switches.)"""
 import glob, os, re, subprocess, sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(os.path.dirname(HERE))
 src = " ".join(open(f, errors="ignore").read() for f in glob.glob(os.path.join(REPO, "collaborative-distillation_amd", "csrc", "*")) +
-               glob.glob(os.path.join(REPO, "collaborative-distillation_amd", "wct_hip", "*.py")) + [os.path.join(REPO, "bench.py")])
+               glob.glob(os.path.join(REPO, "collaborative-distillation_amd", "wct_hip", "*.py")) + [os.path.join(REPO, "bench.py"), os.path.join(REPO, "collaborative-distillation_amd", "build.sh")])
 envs = set(re.findall(r"(WCT_[A-Z0-9_]+)", src))
 keys = set(re.findall(r'strcmp\(key, "([a-z0-9_]+)"\)', src))
 bad = 0
