@@ -189,6 +189,20 @@ int scale_tile_h();
 size_t scale_table_bytes(int H, int W, int oH, int oW, int filter);
 hipError_t launch_scale(const float* a, const float* b, const float* c, float gain, int H, int W, float* out, int oH, int oW, int filter, void* tab,
                         size_t tab_bytes, hipStream_t s);
+// ---- video mode (video.hip; include/wct_hip_video.h).  run / pend: a level's [rs C | rss C*C] inside a clip; flags: (frames, cut)
+//   launch_clip_track      the tracking step T of one level in place on (sum, sumsq), r' also into pend; one launch, C in 1 .. 512
+//   launch_clip_store      prev_content <- the top-left Ho x Wo of content, prev_out <- out (content == NULL: no images), then
+//                          run[0 .. nd) <- pend[0 .. nd) and frames += 1; one launch.  Wo a multiple of 4, the two prev_ images 16-byte aligned
+//   launch_temporal_blend  the blend B in one launch; blend_tile_w / _h: the kernel's output tile
+// (hidden: the library's dynamic symbol table gains the header's entries only)
+__attribute__((visibility("hidden"))) int blend_tile_w();
+__attribute__((visibility("hidden"))) int blend_tile_h();
+__attribute__((visibility("hidden"))) hipError_t launch_clip_track(int C, double n, int decide, double rate, double cut_thr, const double* run, double* pend, double* sum, double* sumsq,
+                             int* flags, hipStream_t s);
+__attribute__((visibility("hidden"))) hipError_t launch_clip_store(const float* content, int Hc, int Wc, const float* out, int Ho, int Wo, float* prev_content, float* prev_out,
+                             const double* pend, double* run, size_t nd, int* flags, hipStream_t s);
+__attribute__((visibility("hidden"))) hipError_t launch_temporal_blend(const float* cur, int Hc, int Wc, const float* prev, const float* sty, const float* pout, int Ho, int Wo, float blend,
+                                 float sigma, int r, const int* cut_flag, float* out, uint8_t* out_hwc, int round_mode, hipStream_t s);
 
 // ---- pitched block copy of floats (rows x width; the sharded cascade's level crops, halo packing and assembly: a planar 3 x H x W image is
 //      3H rows of pitch W)

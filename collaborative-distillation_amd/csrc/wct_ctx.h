@@ -84,6 +84,8 @@ using wct_host::Module;
 using wct_host::ProfRec;
 using wct_host::ResizeAxis;
 
+struct wct_clip;   // the state of one frame sequence (include/wct_hip_video.h; defined in api_video.hip)
+
 struct wct_ctx {
   int device = 0;
   Lane main, side;
@@ -189,6 +191,10 @@ struct wct_ctx {
   int poison = -1;                     // 0..255: every ensure() allocation is filled with this byte; -1: off
   unsigned long long ws_allocs = 0;    // ensure() allocations so far
   bool pair_open = false;              // between wct_content_encode and wct_content_decode: featC / l1img are state
+  // video mode (include/wct_hip_video.h): set ONLY for the duration of wct_stylize_clip -- content_side then passes every level's content
+  // sums through the clip's tracking step.  The clip's memory is the clip's own: no DevBuf of the context, nothing for each_buf
+  wct_clip* track = nullptr;
+  int clip_channels = 0;               // debug key "clip_channels": the channel count of every level of clips created from now on; 0: the loaded encoders'
 
   // EVERY DevBuf of the context, once, with its class: f(buf, owning lane, scratch).  Scratch = no later call is documented to read
   // what an earlier call left there, so the "poison" hook may overwrite it between calls; state must survive (style slots, the
@@ -313,6 +319,8 @@ int stylize_prepared_impl(wct_ctx* ctx, const char* what, const float* content, 
 void free_module(Module& m);
 // api_sharded.hip
 void release_comm(wct_ctx* ctx);   // wct_destroy: destroys a communicator the context owns
+// api_video.hip
+__attribute__((visibility("hidden"))) int clip_track_level(wct_ctx* ctx, wct_clip* clip, int level, int C, double* sum, double* sumsq);   // the tracking step of wct_stylize_clip's frame: nothing committed
 // api_multi.hip
 int apply_labeled_impl(wct_ctx* ctx, const float* feat, int C, long npix, const uint8_t* lab, int K, const double* M, const double* b, float* out);
 

@@ -44,6 +44,11 @@ divisor dL and, where the working size grows, brings the running image up and pu
 --styleMaskPath DIR (with --maskPath; not in the reference; Gatys et al. 2017, section 4) gives the styles label maps of their own: only the
 style pixels with label k enter region k's style statistics (wct_stylize_guided).  --auto_regions K makes both label maps itself, by k-means
 on the style's features of --auto_level (wct_feature_regions), for ordinary content x style pairs; the files carry _auto=<K>.
+--video (not in the reference) treats the picked content files, sorted by name, as the frames of one sequence: per style one clip
+(wct_stylize_clip) tracks the content statistics over the frames (--temporal_rate, reset at a scene cut: --scene_cut) and blends every
+output with the previous one where the content did not move (--temporal_blend, --temporal_sigma, --temporal_radius); the defaults are
+looks, not measurements.  The style is prepared once, the frames run one at a time; --transform and --alpha go with it, the other modes
+and --mode original do not.  One image per frame under the usual name.
 Decoding/encoding files needs Pillow on the host (the reference's own dependency); the GPU library is mandatory: there
 is no CPU fallback.
 """
@@ -145,6 +150,22 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--coarse_style", type=str, default=None,
                    help="with --level_scale: a second style image for the levels whose divisor is > 1 (scale mixing); the other levels "
                         "take the pair's style")
+    # not in the reference: video mode, temporally stable stylisation of a frame sequence (include/wct_hip_video.h)
+    p.add_argument("--video", action="store_true",
+                   help="the picked content files, sorted by name, are the frames of ONE sequence: content statistics are tracked over "
+                        "the frames and the output is blended with the previous one where the content did not move; one clip per style")
+    p.add_argument("--temporal_rate", type=float, default=None,
+                   help="with --video: weight of the new frame in the tracked content statistics, in (0, 1] (default 0.25; 1 = per-frame "
+                        "statistics); a look, not a measurement")
+    p.add_argument("--scene_cut", type=float, default=None,
+                   help="with --video: a frame whose mean level-5 feature moved by more than this many running variances starts afresh "
+                        "(default 0.5; inf = never, 0 = every frame)")
+    p.add_argument("--temporal_blend", type=float, default=None,
+                   help="with --video: weight of the previous output where the content stands still, in [0, 1) (default 0.6; 0 = off)")
+    p.add_argument("--temporal_sigma", type=float, default=None,
+                   help="with --video: the content difference (images in [0, 1]) at which the blend has faded to exp(-1/2) (default 0.05)")
+    p.add_argument("--temporal_radius", type=int, default=None,
+                   help="with --video: radius in pixels of the window the content difference is averaged over, 0 .. 8 (default 2)")
     return p
 
 
@@ -610,6 +631,103 @@ def run_scale(args, wct, pairs, content_dir, style_dir, logprinter) -> float:
         avg += dt
         logprinter("Elapsed time is: %.4f seconds" % dt)
     return avg
+
+
+VIDEO_FLAGS = (("temporal_rate", "--temporal_rate"), ("scene_cut", "--scene_cut"), ("temporal_blend", "--temporal_blend"),
+               ("temporal_sigma", "--temporal_sigma"), ("temporal_radius", "--temporal_radius"))
+
+
+def video_frames(content_dir: str, content_mark: str = ".") -> List[str]:
+    """The frames of --video: the picked content files sorted by NAME (os.listdir's order is the file system's)."""
+    return sorted(x for x in os.listdir(content_dir) if is_image_file(x) and content_mark in x)
+
+
+def check_video_args(args, frame_shapes=None) -> None:
+    """--video and its five parameters: a plain content x style run of the affine cascade with a model the clip supports; --transform,
+    --alpha, --numpy and --round go with it.  Fills in the defaults.  frame_shapes: [(file, (H, W)), ...] of the frames after
+    --content_size, when known -- one clip has one size, so a frame that differs from the first is refused by name."""
+    from .lib import CLIP_BLEND, CLIP_CUT, CLIP_MAX_RADIUS, CLIP_RADIUS, CLIP_RATE, CLIP_SIGMA
+    if not getattr(args, "video", False):
+        for attr, name in VIDEO_FLAGS:
+            if getattr(args, attr, None) is not None:
+                raise ValueError("%s does nothing without --video" % name)
+        return
+    clash = [name for flag, name in ((args.synthesis, "--synthesis"), (args.maskPath is not None, "--maskPath"),
+                                     (args.interp_styles is not None, "--interp_styles"), (args.weightPath is not None, "--weightPath"),
+                                     (getattr(args, "swap_level", None), "--swap_level"), (getattr(args, "level_scale", None), "--level_scale"),
+                                     (getattr(args, "auto_regions", None), "--auto_regions"),
+                                     (getattr(args, "preserve_color", None), "--preserve_color"),
+                                     (getattr(args, "smooth_radius", 0), "--smooth_radius")) if flag]
+    if clash:
+        raise ValueError("--video does not mix with %s" % ", ".join(clash))
+    if args.mode == "original" or args.mode is None:
+        raise ValueError("--video needs --mode 16x or 16x_kd2sd: the un-pruned models (--mode original) may solve a frame twice, which "
+                         "would track it twice (wct_stylize_clip refuses them)")
+    if args.num_run != 1:
+        raise ValueError("--video runs the cascade once per frame (--num_run 1), got %r" % (args.num_run,))
+    for attr, default in (("temporal_rate", CLIP_RATE), ("scene_cut", CLIP_CUT), ("temporal_blend", CLIP_BLEND), ("temporal_sigma", CLIP_SIGMA),
+                          ("temporal_radius", CLIP_RADIUS)):
+        if getattr(args, attr, None) is None:
+            setattr(args, attr, default)
+    if not (0.0 < args.temporal_rate <= 1.0):
+        raise ValueError("--temporal_rate: a value in (0, 1] expected, got %r" % (args.temporal_rate,))
+    if not (args.scene_cut >= 0.0):
+        raise ValueError("--scene_cut: a value >= 0 (or inf) expected, got %r" % (args.scene_cut,))
+    if not (0.0 <= args.temporal_blend < 1.0):
+        raise ValueError("--temporal_blend: a value in [0, 1) expected, got %r" % (args.temporal_blend,))
+    if not (0.0 < args.temporal_sigma < float("inf")):
+        raise ValueError("--temporal_sigma: a finite value > 0 expected, got %r" % (args.temporal_sigma,))
+    if not (0 <= args.temporal_radius <= CLIP_MAX_RADIUS):
+        raise ValueError("--temporal_radius: 0 .. %d expected, got %r" % (CLIP_MAX_RADIUS, args.temporal_radius))
+    if frame_shapes:
+        first_file, first = frame_shapes[0]
+        for name, shape in frame_shapes[1:]:
+            if tuple(shape) != tuple(first):
+                raise ValueError("--video: frame %s is %dx%d, the first frame %s is %dx%d -- one sequence has one size"
+                                 % (name, shape[1], shape[0], first_file, first[1], first[0]))
+
+
+def run_video(args, wct, content_dir, style_dir, logprinter) -> Tuple[float, int]:
+    """--video: per style one clip -- the style prepared once, then the frames in name order through wct_stylize_clip, one at a time;
+    one image per (frame, style) under the usual name.  Returns (summed per-frame time, frames written)."""
+    import torch
+    from PIL import Image
+    frames = video_frames(content_dir, args.picked_content_mark)
+    styles = sorted(x for x in os.listdir(style_dir) if is_image_file(x) and args.picked_style_mark in x)
+    logprinter("Number of frames: %s, styles: %s" % (len(frames), len(styles)))
+    if not frames or not styles:
+        return 0.0, 0
+    shapes = []
+    for f in frames:
+        with Image.open(os.path.join(content_dir, f)) as im:
+            shapes.append((f, resized_shape(im.size[1], im.size[0], args.content_size)))
+    check_video_args(args, shapes)
+    H, W = shapes[0][1]
+    avg, n = 0.0, 0
+    for sfile in styles:
+        s_u8 = torch.from_numpy(load_rgb_u8(os.path.join(style_dir, sfile))).pin_memory().cuda(non_blocking=True)
+        wct.style_prepare(_to_tensor(wct, s_u8, args.style_size))
+        clip = wct.clip(H, W, args.temporal_rate, args.scene_cut, args.temporal_blend, args.temporal_sigma, args.temporal_radius)
+        try:
+            for i, cfile in enumerate(frames):
+                imname = pair_name(cfile, sfile)
+                logprinter("\n" + "*" * 30 + ' #%s: Transferring "%s" (video: rate %g, cut %g, blend %g)' % (
+                    i, imname, args.temporal_rate, args.scene_cut, args.temporal_blend))
+                c_u8 = torch.from_numpy(load_rgb_u8(os.path.join(content_dir, cfile))).pin_memory().cuda(non_blocking=True)
+                t0 = time.time()
+                c_f32 = _to_tensor(wct, c_u8, args.content_size)
+                _, hwc = clip.stylize(c_f32, args.alpha, u8=True, round_mode=args.round_mode)
+                out = hwc.cpu().numpy()   # .cpu() syncs
+                if wct.saturation_count(reset=True):
+                    logprinter("WARNING: f16x3 range exceeded in this frame: its result deviates from the fp32 reference")
+                Image.fromarray(out).save(out_name(args, imname))
+                dt = time.time() - t0
+                avg += dt
+                n += 1
+                logprinter("Elapsed time is: %.4f seconds" % dt)
+        finally:
+            clip.close()
+    return avg, n
 
 
 def _finish_u8(wct, args, res, c_f32):
@@ -1088,6 +1206,7 @@ def main(argv: Optional[List[str]] = None) -> int:
     check_swap_args(args)
     check_scale_args(args)
     check_auto_args(args)
+    check_video_args(args)
     os.makedirs(args.outf, exist_ok=True)
     logprinter = LogPrinter(args.debug, os.path.join(args.outf, "log_%s_%s.txt" % (args.log_mark, args.mode)))
     logprinter(sorted(vars(args).items()))
@@ -1121,6 +1240,15 @@ def main(argv: Optional[List[str]] = None) -> int:
         avg, n = run_interp(args, wct, content_dir, logprinter)
         if n:
             logprinter("Processed %d images. Average processing time per image is: %.4f seconds" % (n, avg / n))
+        return 0
+    if args.video:
+        from .wct import WCT
+        wct = WCT(args)
+        if args.pipeline > 0:
+            logprinter("--pipeline is ignored with --video: a sequence is stylised frame by frame, each against the one before")
+        avg, n = run_video(args, wct, content_dir, style_dir, logprinter)
+        if n:
+            logprinter("Processed %d images. Average processing time per frame is: %.4f seconds" % (n, avg / n))
         return 0
     pairs = list_pairs(content_dir, style_dir, args.picked_content_mark, args.picked_style_mark)
 

@@ -71,6 +71,12 @@ KMEANS_MAX_K = 8                                                    # WCT_KMEANS
 KMEANS_MAX_ITERS = 64                                               # WCT_KMEANS_MAX_ITERS
 KMEANS_DEAD_VARIANCE = 1e-12                                        # WCT_KMEANS_DEAD_VARIANCE
 
+# every symbol include/wct_hip_video.h declares (video mode: tracked statistics and the temporal blend of a frame sequence); bound from the same libwct_hip.so
+SYMBOLS_VIDEO = ["wct_clip_bytes", "wct_clip_create", "wct_clip_destroy", "wct_clip_reset", "wct_clip_export", "wct_moments_track", "wct_temporal_blend",
+                 "wct_stylize_clip"]
+CLIP_MAX_RADIUS = 8                                                 # WCT_CLIP_MAX_RADIUS
+CLIP_RATE, CLIP_CUT, CLIP_BLEND, CLIP_SIGMA, CLIP_RADIUS = 0.25, 0.5, 0.6, 0.05, 2   # WCT_CLIP_*: the command line's defaults
+
 
 class WctLayer(ctypes.Structure):
     _fields_ = [("cin", c_int), ("cout", c_int), ("pool_after", c_int), ("up_after", c_int),
@@ -84,6 +90,11 @@ class WctProfEntry(ctypes.Structure):
 
 class WctP2P(ctypes.Structure):
     _fields_ = [("peer", c_int), ("is_send", c_int), ("buf", c_void_p), ("bytes", c_size_t)]
+
+
+class WctClipParams(ctypes.Structure):
+    """include/wct_hip_video.h wct_clip_params."""
+    _fields_ = [("rate", c_double), ("cut", c_double), ("blend", c_float), ("sigma", c_float), ("radius", c_int)]
 
 
 ALL_REDUCE_FN = ctypes.CFUNCTYPE(c_int, c_void_p, c_void_p, c_size_t, c_void_p)          # (user, buf, count, stream)
@@ -211,6 +222,15 @@ def load() -> ctypes.CDLL:
     lib.wct_kmeans_assign.argtypes = [c_void_p, vp, c_int, c_int, c_int, vp, vp, vp, c_int, vp, vp, vp, vp, vp]
     lib.wct_kmeans_seed.argtypes = [c_void_p, vp, c_int, c_int, c_int, vp, vp, c_int, vp, vp]
     lib.wct_feature_regions.argtypes = [c_void_p, c_int, vp, c_int, c_int, vp, c_int, c_int, c_int, c_int, vp, vp, vp]
+    lib.wct_clip_bytes.argtypes = [c_int, c_int, ip, POINTER(c_size_t)]
+    lib.wct_clip_create.argtypes = [c_void_p, c_int, c_int, POINTER(WctClipParams), POINTER(c_void_p)]
+    lib.wct_clip_destroy.argtypes = [c_void_p, c_void_p]
+    lib.wct_clip_destroy.restype = None
+    lib.wct_clip_reset.argtypes = [c_void_p, c_void_p]
+    lib.wct_clip_export.argtypes = [c_void_p, c_void_p, c_int, vp, vp, vp]
+    lib.wct_moments_track.argtypes = [c_void_p, c_void_p, c_int, c_int, vp, vp]
+    lib.wct_temporal_blend.argtypes = [c_void_p, vp, c_int, c_int, vp, vp, vp, c_int, c_int, c_float, c_float, c_int, vp, vp, vp, c_int]
+    lib.wct_stylize_clip.argtypes = [c_void_p, c_void_p, vp, c_int, c_int, c_float, vp, vp, c_int, ip, ip]
     lib.wct_set_transform.argtypes = [c_void_p, c_int]
     lib.wct_get_transform.argtypes = [c_void_p, ip]
     lib.wct_transform_solve.argtypes = [c_void_p, c_int, c_int, c_double, vp, vp, vp, c_double, vp, vp, ip]

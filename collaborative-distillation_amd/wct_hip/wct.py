@@ -1110,6 +1110,51 @@ class WCT:
             self._style_keep = s      # the side stream reads it asynchronously
         return out.view(-1)[: 3 * ho.value * wo.value].view(1, 3, ho.value, wo.value)
 
+    # ------------------------------------------------------------------ video mode (include/wct_hip_video.h)
+    def clip(self, H: int, W: int, rate: float = _lib.CLIP_RATE, cut: float = _lib.CLIP_CUT, blend: float = _lib.CLIP_BLEND,
+             sigma: float = _lib.CLIP_SIGMA, radius: int = _lib.CLIP_RADIUS) -> "Clip":
+        """The state of one sequence of H x W frames (wct_clip_create): content statistics tracked over time at `rate` with a
+        scene-cut reset above the distance `cut`, and a recursive blend of the output with weight `blend` where the content did not
+        move (`sigma`, `radius`).  Allocates everything once; frames then go through Clip.stylize()."""
+        return Clip(self, int(H), int(W), float(rate), float(cut), float(blend), float(sigma), int(radius))
+
+    @torch.no_grad()
+    def moments_track(self, clip: "Clip", level: int, sum_c: torch.Tensor, sumsq_c: torch.Tensor, decide: bool = False):
+        """The tracking step of one level IN PLACE on fp64 device sums (wct_moments_track), committed at once: r' = c on a cut (decided
+        here when `decide`, else the clip's stored flag), else r + rate (c - r); returns (sum_c, sumsq_c), now holding r'."""
+        C = clip.channels(level)
+        for t, numel, what in ((sum_c, C, "sum_c"), (sumsq_c, C * C, "sumsq_c")):
+            if t.dtype != torch.float64 or not t.is_cuda or t.device.index != self.device or not t.is_contiguous() or t.numel() != numel:
+                raise ValueError("moments_track: %s must be a contiguous fp64 tensor on cuda:%d with %d values" % (what, self.device, numel))
+        self._stream()
+        self._chk(self._lib.wct_moments_track(self._ctx, clip._handle(), int(level), int(bool(decide)), sum_c.data_ptr(), sumsq_c.data_ptr()))
+        return sum_c, sumsq_c
+
+    @torch.no_grad()
+    def temporal_blend(self, content: torch.Tensor, prev_content: torch.Tensor, stylised: torch.Tensor, prev_out: torch.Tensor,
+                       blend: float = _lib.CLIP_BLEND, sigma: float = _lib.CLIP_SIGMA, radius: int = _lib.CLIP_RADIUS,
+                       cut_flag: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, u8: bool = False, round_mode: int = 0):
+        """out = s + w (p - s), w = blend exp(-d / (2 sigma^2)), d = the mean squared difference of the content (its top-left
+        Ho x Wo) and prev_content over a (2 radius + 1)^2 window (wct_temporal_blend); a non-zero `cut_flag` (an int32 device
+        scalar) gives s.  Returns fp32 [1,3,Ho,Wo]; with u8=True (that, uint8 [Ho,Wo,3]), the bytes equal to to_u8(out, round_mode)."""
+        c, q, s, p = self._img(content), self._img(prev_content), self._img(stylised), self._img(prev_out)
+        Hc, Wc, Ho, Wo = int(c.shape[1]), int(c.shape[2]), int(s.shape[1]), int(s.shape[2])
+        if tuple(q.shape) != (3, Ho, Wo) or tuple(p.shape) != (3, Ho, Wo):
+            raise ValueError("temporal_blend: prev_content %s and prev_out %s must have the stylised image's shape %s"
+                             % (tuple(q.shape), tuple(p.shape), tuple(s.shape)))
+        if cut_flag is not None and (cut_flag.dtype != torch.int32 or not cut_flag.is_cuda or cut_flag.numel() != 1):
+            raise ValueError("temporal_blend: cut_flag must be an int32 device tensor with one value")
+        out = self._out_like(out, "temporal_blend", 3 * Ho * Wo)
+        if out is None:
+            out = torch.empty((1, 3, Ho, Wo), device=s.device, dtype=torch.float32)
+        hwc = torch.empty((Ho, Wo, 3), device=s.device, dtype=torch.uint8) if u8 else None
+        self._stream()
+        self._chk(self._lib.wct_temporal_blend(self._ctx, c.data_ptr(), Hc, Wc, q.data_ptr(), s.data_ptr(), p.data_ptr(), Ho, Wo, float(blend),
+                                               float(sigma), int(radius), cut_flag.data_ptr() if cut_flag is not None else None, out.data_ptr(),
+                                               hwc.data_ptr() if u8 else None, int(round_mode)))
+        out = out.view(1, 3, Ho, Wo)
+        return (out, hwc) if u8 else out
+
     # ------------------------------------------------------------------ spatial control (regions)
     def _labels(self, labels: torch.Tensor, h: int, w: int) -> torch.Tensor:
         if labels.dtype != torch.uint8 or tuple(labels.shape) != (h, w):
@@ -1430,6 +1475,80 @@ class WCT:
         self._chk(self._lib.wct_profile_read(self._ctx, buf, 64, byref(n)))
         return [{"name": buf[i].name.decode(), "ms": buf[i].ms, "flops": buf[i].flops, "bytes": buf[i].bytes,
                  "launches": buf[i].launches} for i in range(min(n.value, 64))]
+
+
+class Clip:
+    """One frame sequence of a WCT engine (include/wct_hip_video.h wct_clip; made by WCT.clip).  The state -- tracked content sums,
+    the previous frame's content and output -- lives in the clip, not in the engine: other calls of the engine between frames
+    change nothing here, and the clip changes nothing of theirs.  close() (or garbage collection) frees it; close it before the
+    engine goes."""
+
+    def __init__(self, owner: WCT, H: int, W: int, rate: float, cut: float, blend: float, sigma: float, radius: int):
+        self.owner, self.H, self.W = owner, H, W
+        self.params = _lib.WctClipParams(rate, cut, blend, sigma, radius)
+        self._clip = c_void_p()
+        owner._chk(owner._lib.wct_clip_create(owner._ctx, H, W, byref(self.params), byref(self._clip)))
+        self.Ho, self.Wo = H // 16 * 16, W // 16 * 16
+
+    def _handle(self) -> c_void_p:
+        if not self._clip.value:
+            raise RuntimeError("the clip is closed")
+        return self._clip
+
+    def channels(self, level: int) -> int:
+        return self.owner._feature_channels(level)
+
+    @torch.no_grad()
+    def stylize(self, content: torch.Tensor, alpha: Optional[float] = None, out: Optional[torch.Tensor] = None, u8: bool = False,
+                round_mode: int = 0):
+        """The next frame (wct_stylize_clip) against the engine's prepared style (style_prepare / style_import): fp32 [1,3,Ho,Wo]; with
+        u8=True (that, uint8 [Ho,Wo,3]).  Asynchronous, allocation-free after the first frame, and capturable into one HIP graph
+        when `content` and `out` are the caller's fixed buffers."""
+        o = self.owner
+        alpha = o.alpha if alpha is None else float(alpha)
+        c = o._img(content)
+        H, W = int(c.shape[1]), int(c.shape[2])
+        out = o._out_like(out, "Clip.stylize", 3 * self.Ho * self.Wo)
+        if out is None:
+            out = torch.empty((1, 3, self.Ho, self.Wo), device=c.device, dtype=torch.float32)
+        hwc = torch.empty((self.Ho, self.Wo, 3), device=c.device, dtype=torch.uint8) if u8 else None
+        ho, wo = c_int(), c_int()
+        o._stream()
+        o._chk(o._lib.wct_stylize_clip(o._ctx, self._handle(), c.data_ptr(), H, W, alpha, out.data_ptr(), hwc.data_ptr() if u8 else None,
+                                       int(round_mode), byref(ho), byref(wo)))
+        out = out.view(1, 3, self.Ho, self.Wo)
+        return (out, hwc) if u8 else out
+
+    def reset(self) -> None:
+        """The next frame is a first frame: tracked statistics and the previous output are not used (asynchronous)."""
+        o = self.owner
+        o._stream()
+        o._chk(o._lib.wct_clip_reset(o._ctx, self._handle()))
+
+    @torch.no_grad()
+    def export(self, level: int):
+        """(sum [C], sumsq [C,C], flags [2] = (frames, cut)) of `level` as device tensors, in stream order (wct_clip_export)."""
+        o = self.owner
+        C = self.channels(level)
+        s = torch.empty(C, device=o.stats_device, dtype=torch.float64)
+        ss = torch.empty(C, C, device=o.stats_device, dtype=torch.float64)
+        flags = torch.empty(2, device=o.stats_device, dtype=torch.int32)
+        o._stream()
+        o._chk(o._lib.wct_clip_export(o._ctx, self._handle(), int(level), s.data_ptr(), ss.data_ptr(), flags.data_ptr()))
+        return s, ss, flags
+
+    def close(self) -> None:
+        if getattr(self, "_clip", None) is not None and self._clip.value:
+            o = self.owner
+            alive = getattr(o, "_ctx", None) is not None and o._ctx.value
+            o._lib.wct_clip_destroy(o._ctx if alive else None, self._clip)   # the allocation is the clip's own: freed either way
+            self._clip = c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 @torch.no_grad()
