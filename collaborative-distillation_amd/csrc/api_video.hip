@@ -1,24 +1,9 @@
 // Video mode of the C ABI (include/wct_hip_video.h): the clip object, the tracking step, the temporal blend and the one-call frame entry.
 // Host orchestration only; the kernels are in video.hip.
 #include "../../include/wct_hip_video.h"
-#include "wct_ctx.h"
+#include "wct_clip.h"
 
 using namespace wct_host;
-
-// The state of one frame sequence: ONE device allocation, laid out as the header's Definitions say.
-struct wct_clip {
-  wct_ctx* owner = nullptr;
-  int H = 0, W = 0, Ho = 0, Wo = 0;
-  wct_clip_params p{};
-  int C[6] = {0, 0, 0, 0, 0, 0};        // by level
-  double n[6] = {0, 0, 0, 0, 0, 0};     // pixels of the level's feature map
-  size_t off[6] = {0, 0, 0, 0, 0, 0};   // doubles in front of the level inside a block of sums
-  size_t nd = 0;                        // doubles of one block of sums
-  void* base = nullptr;
-  double *run = nullptr, *pend = nullptr;
-  int* flags = nullptr;                 // frames, cut
-  float *prev_content = nullptr, *prev_out = nullptr, *stylised = nullptr;
-};
 
 namespace {
 size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
@@ -50,17 +35,16 @@ int params_check(wct_ctx* ctx, const char* who, double rate, double cut, float b
   return WCT_OK;
 }
 
-int clip_check(wct_ctx* ctx, const char* who, const wct_clip* clip) {
-  if (!clip) return fail(ctx, WCT_ERR_INVALID, "%s: NULL clip", who);
-  if (clip->owner != ctx) return fail(ctx, WCT_ERR_INVALID, "%s: the clip belongs to another context", who);
-  return WCT_OK;
-}
-
+// mv == NULL: video mode's blend; else the compensated one (include/wct_hip_motion.h), profiled under a name of its own
 int blend_impl(wct_ctx* ctx, const float* cur, int Hc, int Wc, const float* prev, const float* sty, const float* pout, int Ho, int Wo, float blend,
-               float sigma, int radius, const int* cut_flag, float* out_planar, uint8_t* out_hwc, int round_mode) {
+               float sigma, int radius, const int* cut_flag, float* out_planar, uint8_t* out_hwc, int round_mode, const int16_t* mv = nullptr) {
   const double px = (double)Ho * Wo;
-  ProfScope ps(ctx, ctx->main.stream, "temporal_blend", (9.0 + 4.0 * (2 * radius + 1) + 12.0) * px, (60.0 + (out_hwc ? 3.0 : 0.0)) * px);
-  HIPCHK(ctx, launch_temporal_blend(cur, Hc, Wc, prev, sty, pout, Ho, Wo, blend, sigma, radius, cut_flag, out_planar, out_hwc, round_mode, ctx->main.stream));
+  ProfScope ps(ctx, ctx->main.stream, mv ? "motion_blend" : "temporal_blend", (9.0 + 4.0 * (2 * radius + 1) + 12.0) * px, (60.0 + (out_hwc ? 3.0 : 0.0)) * px);
+  if (mv)
+    HIPCHK(ctx, launch_motion_blend(cur, Hc, Wc, prev, sty, pout, Ho, Wo, blend, sigma, radius, cut_flag, out_planar, out_hwc, round_mode, mv,
+                                    (Wo + WCT_MOTION_BLOCK - 1) / WCT_MOTION_BLOCK, ctx->main.stream));
+  else
+    HIPCHK(ctx, launch_temporal_blend(cur, Hc, Wc, prev, sty, pout, Ho, Wo, blend, sigma, radius, cut_flag, out_planar, out_hwc, round_mode, ctx->main.stream));
   return WCT_OK;
 }
 
@@ -73,6 +57,31 @@ struct TrackScope {
 }  // namespace
 
 namespace wct_host {
+int clip_check(wct_ctx* ctx, const char* who, const wct_clip* clip) {
+  if (!clip) return fail(ctx, WCT_ERR_INVALID, "%s: NULL clip", who);
+  if (clip->owner != ctx) return fail(ctx, WCT_ERR_INVALID, "%s: the clip belongs to another context", who);
+  return WCT_OK;
+}
+
+int blend_entry(wct_ctx* ctx, const char* who, const float* cur_content, int Hc, int Wc, const float* prev_content, const float* stylised,
+                const float* prev_out, int Ho, int Wo, float blend, float sigma, int radius, const int* cut_flag_dev, float* out_planar, uint8_t* out_hwc,
+                int round_mode, const int16_t* mv) {
+  if (!cur_content || !prev_content || !stylised || !prev_out || !out_planar) return fail(ctx, WCT_ERR_INVALID, "%s: NULL image", who);
+  if (Ho < 1 || Wo < 1 || Ho > Hc || Wo > Wc)
+    return fail(ctx, WCT_ERR_INVALID, "%s: result %dx%d must be non-empty and no larger than the content %dx%d", who, Ho, Wo, Hc, Wc);
+  if (int rc = params_check(ctx, who, 1.0, 0.0, blend, sigma, radius)) return rc;
+  if (round_mode != 0 && round_mode != 1) return fail(ctx, WCT_ERR_INVALID, "%s: round_mode 0 or 1 expected, got %d", who, round_mode);
+  const size_t img = (size_t)3 * Ho * Wo * sizeof(float), cimg = (size_t)3 * Hc * Wc * sizeof(float), u8 = (size_t)3 * Ho * Wo;
+  const size_t field = mv ? (size_t)((Ho + WCT_MOTION_BLOCK - 1) / WCT_MOTION_BLOCK) * ((Wo + WCT_MOTION_BLOCK - 1) / WCT_MOTION_BLOCK) * 2 * sizeof(int16_t) : 0;
+  const void* ins[5] = {cur_content, prev_content, stylised, prev_out, mv};
+  const size_t in_bytes[5] = {cimg, img, img, img, field};
+  for (int i = 0; i < (mv ? 5 : 4); ++i)
+    if (ranges_overlap(out_planar, img, ins[i], in_bytes[i]) || (out_hwc && ranges_overlap(out_hwc, u8, ins[i], in_bytes[i])))
+      return fail(ctx, WCT_ERR_INVALID, "%s: an output overlaps an input (the kernel reads a halo: nothing may alias)", who);
+  if (out_hwc && ranges_overlap(out_hwc, u8, out_planar, img)) return fail(ctx, WCT_ERR_INVALID, "%s: out_hwc overlaps out_planar", who);
+  return blend_impl(ctx, cur_content, Hc, Wc, prev_content, stylised, prev_out, Ho, Wo, blend, sigma, radius, cut_flag_dev, out_planar, out_hwc, round_mode, mv);
+}
+
 int clip_track_level(wct_ctx* ctx, wct_clip* clip, int level, int C, double* sum, double* sumsq) {
   if (C != clip->C[level]) return fail(ctx, WCT_ERR_STATE, "clip: level %d has %d channels, the clip was made for %d (a module was reloaded)", level, C, clip->C[level]);
   const double nel = (double)C + (double)C * C;
@@ -147,6 +156,7 @@ void wct_clip_destroy(wct_ctx* ctx, wct_clip* clip) {
       (void)hipStreamSynchronize(ctx->side.stream);
       if (ctx->track == clip) ctx->track = nullptr;
     }
+    motion_release(clip);
     if (clip->base) (void)hipFree(clip->base);
   }
   delete clip;
@@ -199,19 +209,8 @@ int wct_temporal_blend(wct_ctx* ctx, const float* cur_content, int Hc, int Wc, c
                        int Ho, int Wo, float blend, float sigma, int radius, const int* cut_flag_dev, float* out_planar, uint8_t* out_hwc, int round_mode) {
   if (!ctx) return WCT_ERR_INVALID;
   WCT_GUARD(ctx);
-  if (!cur_content || !prev_content || !stylised || !prev_out || !out_planar) return fail(ctx, WCT_ERR_INVALID, "wct_temporal_blend: NULL image");
-  if (Ho < 1 || Wo < 1 || Ho > Hc || Wo > Wc)
-    return fail(ctx, WCT_ERR_INVALID, "wct_temporal_blend: result %dx%d must be non-empty and no larger than the content %dx%d", Ho, Wo, Hc, Wc);
-  if (int rc = params_check(ctx, "wct_temporal_blend", 1.0, 0.0, blend, sigma, radius)) return rc;
-  if (round_mode != 0 && round_mode != 1) return fail(ctx, WCT_ERR_INVALID, "wct_temporal_blend: round_mode 0 or 1 expected, got %d", round_mode);
-  const size_t img = (size_t)3 * Ho * Wo * sizeof(float), cimg = (size_t)3 * Hc * Wc * sizeof(float), u8 = (size_t)3 * Ho * Wo;
-  const void* ins[4] = {cur_content, prev_content, stylised, prev_out};
-  const size_t in_bytes[4] = {cimg, img, img, img};
-  for (int i = 0; i < 4; ++i)
-    if (ranges_overlap(out_planar, img, ins[i], in_bytes[i]) || (out_hwc && ranges_overlap(out_hwc, u8, ins[i], in_bytes[i])))
-      return fail(ctx, WCT_ERR_INVALID, "wct_temporal_blend: an output overlaps an input (the kernel reads a halo: nothing may alias)");
-  if (out_hwc && ranges_overlap(out_hwc, u8, out_planar, img)) return fail(ctx, WCT_ERR_INVALID, "wct_temporal_blend: out_hwc overlaps out_planar");
-  return blend_impl(ctx, cur_content, Hc, Wc, prev_content, stylised, prev_out, Ho, Wo, blend, sigma, radius, cut_flag_dev, out_planar, out_hwc, round_mode);
+  return blend_entry(ctx, "wct_temporal_blend", cur_content, Hc, Wc, prev_content, stylised, prev_out, Ho, Wo, blend, sigma, radius, cut_flag_dev, out_planar,
+                     out_hwc, round_mode, nullptr);
 }
 
 int wct_stylize_clip(wct_ctx* ctx, wct_clip* clip, const float* content, int H, int W, float alpha, float* out_planar, uint8_t* out_hwc, int round_mode,
@@ -242,8 +241,13 @@ int wct_stylize_clip(wct_ctx* ctx, wct_clip* clip, const float* content, int H, 
     if (int rc = stylize_prepared_impl(ctx, "wct_stylize_clip", content, H, W, alpha, 1, clip->stylised, &h2, &w2)) return rc;
   }
   if (h2 != ho || w2 != wo) return fail(ctx, WCT_ERR_STATE, "wct_stylize_clip: the cascade returned %dx%d, the clip holds %dx%d", h2, w2, ho, wo);
+  const wct_clip_motion* mo = clip->motion;
+  if (mo)
+    if (int rc = motion_frame_estimate(ctx, clip, content, H, W)) return rc;
   if (int rc = blend_impl(ctx, content, H, W, clip->prev_content, clip->stylised, clip->prev_out, ho, wo, clip->p.blend, clip->p.sigma, clip->p.radius,
-                          clip->flags + 1, out_planar, out_hwc, round_mode)) return rc;
+                          clip->flags + 1, out_planar, out_hwc, round_mode, mo ? mo->mv + mo->lay.lv[0].mv_off : nullptr)) return rc;
+  if (mo)
+    if (int rc = motion_frame_store(ctx, clip)) return rc;
   {
     ProfScope ps(ctx, ctx->main.stream, "clip_store", 0, 48.0 * ho * wo + 16.0 * clip->nd);
     HIPCHK(ctx, launch_clip_store(content, H, W, out_planar, ho, wo, clip->prev_content, clip->prev_out, clip->pend, clip->run, clip->nd, clip->flags,

@@ -114,10 +114,29 @@ __device__ __forceinline__ unsigned to_u8(float v, int round_mode) {
   return (unsigned)x;                  // truncation toward zero
 }
 
-// vec_c / vec_o: the content / the four Ho x Wo images take 16-byte accesses (Wo, and for vec_c Wc, multiples of 4; aligned bases)
+// Four floats of row clamp(y + vy) of an Ho x Wo plane from column x + vx on, each column clamped to the row; the first n exist.  The clamp
+// makes any vector safe; inside the row the four are consecutive at a 4-byte alignment (include/wct_hip_motion.h, Compensated blend).
+__device__ __forceinline__ f32x4 ld4_moved(const float* plane, int Ho, int Wo, int y, int x, int n, int vy, int vx) {
+  const float* row = plane + (size_t)min(max(y + vy, 0), Ho - 1) * Wo;
+  const int xs = x + vx;
+  f32x4 v = {0.f, 0.f, 0.f, 0.f};
+  if (n == 4 && xs >= 0 && xs + 3 < Wo) {
+    __builtin_memcpy(&v, row + xs, sizeof v);
+    return v;
+  }
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+    if (k < n) v[k] = row[min(max(xs + k, 0), Wo - 1)];
+  return v;
+}
+
+// vec_c / vec_o: the content / the four Ho x Wo images take 16-byte accesses (Wo, and for vec_c Wc, multiples of 4; aligned bases).
+// MV: prev and pout are read through the field mv[.][nbx][2] of 8 x 8 blocks -- a group of four pixels starts at a multiple of 4, so it
+// lies in one block and has one vector.  Without MV neither mv nor nbx is looked at: that instantiation is video mode's kernel as it was.
+template <bool MV>
 __global__ __launch_bounds__(256) void temporal_blend_kernel(const float* cur, int Hc, int Wc, const float* prev, const float* sty, const float* pout,
                                                              int Ho, int Wo, float blend, float two_s2, int r, const int* cut_flag, float* out,
-                                                             uint8_t* out_hwc, int round_mode, int vec_c, int vec_o) {
+                                                             uint8_t* out_hwc, int round_mode, int vec_c, int vec_o, const int16_t* mv, int nbx) {
   __shared__ __attribute__((aligned(16))) float e[TB_EH][TB_EW];    // squared content difference over the tile and its halo; 0 outside the image
   __shared__ __attribute__((aligned(16))) float hs[TB_EH][TB_W];    // its horizontal window sums
   const int tid = threadIdx.x, tx0 = blockIdx.x * TB_W, ty0 = blockIdx.y * TB_H;
@@ -139,7 +158,13 @@ __global__ __launch_bounds__(256) void temporal_blend_kernel(const float* cur, i
 #pragma unroll
         for (int ch = 0; ch < 3; ++ch) {
           const f32x4 a = ld4(cur + ch * cplane + (size_t)yy * Wc + xx, m, vec_c);
-          const f32x4 b = ld4(prev + ch * plane + (size_t)yy * Wo + xx, m, vec_o);
+          f32x4 b;
+          if constexpr (MV) {
+            const int16_t* v = mv + ((size_t)(yy >> 3) * nbx + (xx >> 3)) * 2;
+            b = ld4_moved(prev + ch * plane, Ho, Wo, yy, xx, m, v[0], v[1]);
+          } else {
+            b = ld4(prev + ch * plane + (size_t)yy * Wo + xx, m, vec_o);
+          }
           const f32x4 d = a - b;                 // both 0 past the row's end
           acc += d * d;
         }
@@ -176,7 +201,13 @@ __global__ __launch_bounds__(256) void temporal_blend_kernel(const float* cur, i
     if (cut) {
       o[ch] = s;
     } else {
-      const f32x4 p = ld4(pout + ch * plane + o0, n, v4);
+      f32x4 p;
+      if constexpr (MV) {
+        const int16_t* v = mv + ((size_t)(y >> 3) * nbx + (x >> 3)) * 2;
+        p = ld4_moved(pout + ch * plane, Ho, Wo, y, x, n, v[0], v[1]);
+      } else {
+        p = ld4(pout + ch * plane + o0, n, v4);
+      }
 #pragma unroll
       for (int k = 0; k < 4; ++k) o[ch][k] = s[k] + wgt[k] * (p[k] - s[k]);
     }
@@ -241,7 +272,21 @@ hipError_t launch_temporal_blend(const float* cur, int Hc, int Wc, const float* 
   const int vec_c = quad && (Wc & 3) == 0 && aligned16(cur);
   const int vec_o = quad && aligned16(prev) && aligned16(sty) && aligned16(pout) && aligned16(out);
   const dim3 grid((unsigned)((Wo + TB_W - 1) / TB_W), (unsigned)((Ho + TB_H - 1) / TB_H));
-  hipLaunchKernelGGL(temporal_blend_kernel, grid, dim3(256), 0, s, cur, Hc, Wc, prev, sty, pout, Ho, Wo, blend, 2.0f * sigma * sigma, r, cut_flag, out,
-                     out_hwc, round_mode, vec_c, vec_o);
+  hipLaunchKernelGGL(temporal_blend_kernel<false>, grid, dim3(256), 0, s, cur, Hc, Wc, prev, sty, pout, Ho, Wo, blend, 2.0f * sigma * sigma, r, cut_flag,
+                     out, out_hwc, round_mode, vec_c, vec_o, static_cast<const int16_t*>(nullptr), 0);
+  return hipGetLastError();
+}
+
+hipError_t launch_motion_blend(const float* cur, int Hc, int Wc, const float* prev, const float* sty, const float* pout, int Ho, int Wo, float blend,
+                               float sigma, int r, const int* cut_flag, float* out, uint8_t* out_hwc, int round_mode, const int16_t* mv, int nbx,
+                               hipStream_t s) {
+  if (!mv) return launch_temporal_blend(cur, Hc, Wc, prev, sty, pout, Ho, Wo, blend, sigma, r, cut_flag, out, out_hwc, round_mode, s);
+  if (Ho < 1 || Wo < 1 || Ho > Hc || Wo > Wc || r < 0 || r > WCT_CLIP_MAX_RADIUS || nbx != (Wo + 7) / 8) return hipErrorInvalidValue;
+  const int quad = (Wo & 3) == 0;
+  const int vec_c = quad && (Wc & 3) == 0 && aligned16(cur);
+  const int vec_o = quad && aligned16(sty) && aligned16(out);      // prev and pout are gathered: their alignment does not matter
+  const dim3 grid((unsigned)((Wo + TB_W - 1) / TB_W), (unsigned)((Ho + TB_H - 1) / TB_H));
+  hipLaunchKernelGGL(temporal_blend_kernel<true>, grid, dim3(256), 0, s, cur, Hc, Wc, prev, sty, pout, Ho, Wo, blend, 2.0f * sigma * sigma, r, cut_flag,
+                     out, out_hwc, round_mode, vec_c, vec_o, mv, nbx);
   return hipGetLastError();
 }

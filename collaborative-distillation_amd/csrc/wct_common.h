@@ -203,6 +203,24 @@ __attribute__((visibility("hidden"))) hipError_t launch_clip_store(const float* 
                              const double* pend, double* run, size_t nd, int* flags, hipStream_t s);
 __attribute__((visibility("hidden"))) hipError_t launch_temporal_blend(const float* cur, int Hc, int Wc, const float* prev, const float* sty, const float* pout, int Ho, int Wo, float blend,
                                  float sigma, int r, const int* cut_flag, float* out, uint8_t* out_hwc, int round_mode, hipStream_t s);
+// ---- motion compensation (motion.hip; include/wct_hip_motion.h).  A pyramid is packed bytes: level k at pyr + lv[k].pyr_off, rows of
+// lv[k].pitch bytes (W_k rounded up to a dword, the padding zero).  The fields of all levels share one block of int16: level k at lv[k].mv_off.
+struct MotionLevel { int H, W, pitch, nby, nbx; size_t pyr_off, mv_off; };
+struct MotionLayout { int levels; MotionLevel lv[4]; size_t pyr_bytes, mv_count; };   // pyr_bytes: a multiple of 256; mv_count: int16 values
+//   motion_layout           false: levels outside 1 .. 4 or Ho / Wo < 2^(levels - 1)
+//   launch_motion_pyramid   every level of the luma pyramid of the top-left Ho x Wo of a planar image in ONE launch
+//   launch_motion_unpad     the pitched pyramid as the dense concatenation wct_motion_luma returns; one launch
+//   launch_motion_search    one level of the block search: mv_out of that level from the two pyramids and (below the top level) the
+//                           parent level's field; a non-zero *cut_flag (NULL: 0) writes zeros instead
+//   launch_motion_blend     launch_temporal_blend against the previous images displaced by the level-0 field mv
+__attribute__((visibility("hidden"))) bool motion_layout(int Ho, int Wo, int levels, MotionLayout& l);
+__attribute__((visibility("hidden"))) hipError_t launch_motion_pyramid(const float* img, int Hc, int Wc, const MotionLayout& l, uint8_t* pyr, hipStream_t s);
+__attribute__((visibility("hidden"))) hipError_t launch_motion_unpad(const uint8_t* pyr, const MotionLayout& l, uint8_t* out, hipStream_t s);
+__attribute__((visibility("hidden"))) hipError_t launch_motion_search(const uint8_t* pyr_cur, const uint8_t* pyr_prev, const MotionLayout& l, int level, int range,
+                                                                      int penalty, const int16_t* mv_parent, int16_t* mv_out, const int* cut_flag, hipStream_t s);
+__attribute__((visibility("hidden"))) hipError_t launch_motion_blend(const float* cur, int Hc, int Wc, const float* prev, const float* sty, const float* pout, int Ho,
+                                                                     int Wo, float blend, float sigma, int r, const int* cut_flag, float* out, uint8_t* out_hwc,
+                                                                     int round_mode, const int16_t* mv, int nbx, hipStream_t s);
 
 // ---- pitched block copy of floats (rows x width; the sharded cascade's level crops, halo packing and assembly: a planar 3 x H x W image is
 //      3H rows of pitch W)

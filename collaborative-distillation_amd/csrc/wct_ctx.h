@@ -84,7 +84,7 @@ using wct_host::Module;
 using wct_host::ProfRec;
 using wct_host::ResizeAxis;
 
-struct wct_clip;   // the state of one frame sequence (include/wct_hip_video.h; defined in api_video.hip)
+struct wct_clip;   // the state of one frame sequence (include/wct_hip_video.h; defined in wct_clip.h)
 
 struct wct_ctx {
   int device = 0;
@@ -194,6 +194,8 @@ struct wct_ctx {
   // video mode (include/wct_hip_video.h): set ONLY for the duration of wct_stylize_clip -- content_side then passes every level's content
   // sums through the clip's tracking step.  The clip's memory is the clip's own: no DevBuf of the context, nothing for each_buf
   wct_clip* track = nullptr;
+  // motion compensation (include/wct_hip_motion.h), the standalone entries: [pyramid of cur | pyramid of prev | the coarser levels' fields]
+  DevBuf motionWs;
   int clip_channels = 0;               // debug key "clip_channels": the channel count of every level of clips created from now on; 0: the loaded encoders'
 
   // EVERY DevBuf of the context, once, with its class: f(buf, owning lane, scratch).  Scratch = no later call is documented to read
@@ -207,7 +209,7 @@ struct wct_ctx {
     for (DevBuf* b : {&featS, &tmpT, &wsAsm, &trBuf, &small, &foldW, &foldW16, &eigC, &u8c, &u8s, &u8o, &rsz_tmp, &noise, &colStyle, &colOut, &colWs, &smSums, &smAB, &swFc, &swFs, &swQ, &swK, &swOut, &swIdx, &swRun, &swNorm, &swLab, &packed,
                       &shIn, &shOut, &shNext, &shEdge, &shStyle, &shStats, &shMb,
                       &regLab, &regHist, &regSums, &regMb, &regFeat, &wsRegMom, &wsRegApply,
-                      &blendW, &blendStat, &wsBlendPool, &wsBlendApply, &gdLab, &gdHist, &kmFeatC, &kmFeatS, &kmWs, &kmStat})
+                      &blendW, &blendStat, &wsBlendPool, &wsBlendApply, &gdLab, &gdHist, &kmFeatC, &kmFeatS, &kmWs, &kmStat, &motionWs})
       f(*b, &main, true);
     for (DevBuf* b : {&gdSums, &wsGdMom}) f(*b, &side, true);   // the guided call's style side
     for (DevBuf& b : scF) f(b, &main, true);

@@ -48,7 +48,9 @@ on the style's features of --auto_level (wct_feature_regions), for ordinary cont
 (wct_stylize_clip) tracks the content statistics over the frames (--temporal_rate, reset at a scene cut: --scene_cut) and blends every
 output with the previous one where the content did not move (--temporal_blend, --temporal_sigma, --temporal_radius); the defaults are
 looks, not measurements.  The style is prepared once, the frames run one at a time; --transform and --alpha go with it, the other modes
-and --mode original do not.  One image per frame under the usual name.
+and --mode original do not.  One image per frame under the usual name.  --motion (with --video) estimates a block-matched motion field
+between consecutive frames (--motion_levels, --motion_range, --motion_penalty) and blends against the previous frame displaced by it
+(wct_motion_attach): panning and moving regions keep their strokes as the still ones do.
 Decoding/encoding files needs Pillow on the host (the reference's own dependency); the GPU library is mandatory: there
 is no CPU fallback.
 """
@@ -166,6 +168,16 @@ def build_parser() -> argparse.ArgumentParser:
                    help="with --video: the content difference (images in [0, 1]) at which the blend has faded to exp(-1/2) (default 0.05)")
     p.add_argument("--temporal_radius", type=int, default=None,
                    help="with --video: radius in pixels of the window the content difference is averaged over, 0 .. 8 (default 2)")
+    # not in the reference: motion compensation for video mode (include/wct_hip_motion.h)
+    p.add_argument("--motion", action="store_true",
+                   help="with --video: the blend compares every frame with the previous one displaced by a block-matched motion field, so "
+                        "that panning and moving regions keep their strokes too")
+    p.add_argument("--motion_levels", type=int, default=None,
+                   help="with --motion: levels of the luma pyramid the search runs over, 1 .. 4 (default 4); a look, not a measurement")
+    p.add_argument("--motion_range", type=int, default=None,
+                   help="with --motion: search range at the coarsest level in its pixels, 0 .. 7 (default 4)")
+    p.add_argument("--motion_penalty", type=int, default=None,
+                   help="with --motion: cost per pixel of vector length, in grey levels, 0 .. 255 (default 4)")
     return p
 
 
@@ -687,6 +699,33 @@ def check_video_args(args, frame_shapes=None) -> None:
                                  % (name, shape[1], shape[0], first_file, first[1], first[0]))
 
 
+MOTION_FLAGS = (("motion", "--motion"), ("motion_levels", "--motion_levels"), ("motion_range", "--motion_range"),
+                ("motion_penalty", "--motion_penalty"))
+
+
+def check_motion_args(args) -> None:
+    """--motion and its three parameters: they go with --video only, and the parameters with --motion only.  Fills in the defaults."""
+    from .lib import MOTION_LEVELS, MOTION_MAX_LEVELS, MOTION_MAX_RANGE, MOTION_PENALTY, MOTION_RANGE
+    given = [name for attr, name in MOTION_FLAGS if getattr(args, attr, None) is not None and getattr(args, attr) is not False]
+    if not getattr(args, "video", False):
+        if given:
+            raise ValueError("%s does nothing without --video" % given[0])
+        return
+    if not getattr(args, "motion", False):
+        if given:
+            raise ValueError("%s does nothing without --motion" % given[0])
+        return
+    for attr, default in (("motion_levels", MOTION_LEVELS), ("motion_range", MOTION_RANGE), ("motion_penalty", MOTION_PENALTY)):
+        if getattr(args, attr, None) is None:
+            setattr(args, attr, default)
+    if not (1 <= args.motion_levels <= MOTION_MAX_LEVELS):
+        raise ValueError("--motion_levels: 1 .. %d expected, got %r" % (MOTION_MAX_LEVELS, args.motion_levels))
+    if not (0 <= args.motion_range <= MOTION_MAX_RANGE):
+        raise ValueError("--motion_range: 0 .. %d expected, got %r" % (MOTION_MAX_RANGE, args.motion_range))
+    if not (0 <= args.motion_penalty <= 255):
+        raise ValueError("--motion_penalty: 0 .. 255 expected, got %r" % (args.motion_penalty,))
+
+
 def run_video(args, wct, content_dir, style_dir, logprinter) -> Tuple[float, int]:
     """--video: per style one clip -- the style prepared once, then the frames in name order through wct_stylize_clip, one at a time;
     one image per (frame, style) under the usual name.  Returns (summed per-frame time, frames written)."""
@@ -702,17 +741,20 @@ def run_video(args, wct, content_dir, style_dir, logprinter) -> Tuple[float, int
         with Image.open(os.path.join(content_dir, f)) as im:
             shapes.append((f, resized_shape(im.size[1], im.size[0], args.content_size)))
     check_video_args(args, shapes)
+    check_motion_args(args)
+    motion = dict(levels=args.motion_levels, range=args.motion_range, penalty=args.motion_penalty) if getattr(args, "motion", False) else None
+    motion_note = ", motion: levels %d, range %d, penalty %d" % (args.motion_levels, args.motion_range, args.motion_penalty) if motion else ""
     H, W = shapes[0][1]
     avg, n = 0.0, 0
     for sfile in styles:
         s_u8 = torch.from_numpy(load_rgb_u8(os.path.join(style_dir, sfile))).pin_memory().cuda(non_blocking=True)
         wct.style_prepare(_to_tensor(wct, s_u8, args.style_size))
-        clip = wct.clip(H, W, args.temporal_rate, args.scene_cut, args.temporal_blend, args.temporal_sigma, args.temporal_radius)
+        clip = wct.clip(H, W, args.temporal_rate, args.scene_cut, args.temporal_blend, args.temporal_sigma, args.temporal_radius, motion=motion)
         try:
             for i, cfile in enumerate(frames):
                 imname = pair_name(cfile, sfile)
-                logprinter("\n" + "*" * 30 + ' #%s: Transferring "%s" (video: rate %g, cut %g, blend %g)' % (
-                    i, imname, args.temporal_rate, args.scene_cut, args.temporal_blend))
+                logprinter("\n" + "*" * 30 + ' #%s: Transferring "%s" (video: rate %g, cut %g, blend %g%s)' % (
+                    i, imname, args.temporal_rate, args.scene_cut, args.temporal_blend, motion_note))
                 c_u8 = torch.from_numpy(load_rgb_u8(os.path.join(content_dir, cfile))).pin_memory().cuda(non_blocking=True)
                 t0 = time.time()
                 c_f32 = _to_tensor(wct, c_u8, args.content_size)
@@ -1207,6 +1249,7 @@ def main(argv: Optional[List[str]] = None) -> int:
     check_scale_args(args)
     check_auto_args(args)
     check_video_args(args)
+    check_motion_args(args)
     os.makedirs(args.outf, exist_ok=True)
     logprinter = LogPrinter(args.debug, os.path.join(args.outf, "log_%s_%s.txt" % (args.log_mark, args.mode)))
     logprinter(sorted(vars(args).items()))

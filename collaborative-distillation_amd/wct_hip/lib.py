@@ -77,6 +77,11 @@ SYMBOLS_VIDEO = ["wct_clip_bytes", "wct_clip_create", "wct_clip_destroy", "wct_c
 CLIP_MAX_RADIUS = 8                                                 # WCT_CLIP_MAX_RADIUS
 CLIP_RATE, CLIP_CUT, CLIP_BLEND, CLIP_SIGMA, CLIP_RADIUS = 0.25, 0.5, 0.6, 0.05, 2   # WCT_CLIP_*: the command line's defaults
 
+# every symbol include/wct_hip_motion.h declares (motion compensation for video mode: block matching, the warped blend); bound from the same libwct_hip.so
+SYMBOLS_MOTION = ["wct_motion_shape", "wct_motion_luma", "wct_motion_estimate", "wct_motion_blend", "wct_motion_attach", "wct_motion_export"]
+MOTION_BLOCK, MOTION_MAX_LEVELS, MOTION_MAX_RANGE = 8, 4, 7         # WCT_MOTION_BLOCK, WCT_MOTION_MAX_LEVELS, WCT_MOTION_MAX_RANGE
+MOTION_LEVELS, MOTION_RANGE, MOTION_PENALTY = 4, 4, 4               # WCT_MOTION_*: the command line's defaults
+
 
 class WctLayer(ctypes.Structure):
     _fields_ = [("cin", c_int), ("cout", c_int), ("pool_after", c_int), ("up_after", c_int),
@@ -97,7 +102,12 @@ class WctClipParams(ctypes.Structure):
     _fields_ = [("rate", c_double), ("cut", c_double), ("blend", c_float), ("sigma", c_float), ("radius", c_int)]
 
 
-ALL_REDUCE_FN = ctypes.CFUNCTYPE(c_int, c_void_p, c_void_p, c_size_t, c_void_p)          # (user, buf, count, stream)
+class WctMotionParams(ctypes.Structure):
+    """include/wct_hip_motion.h wct_motion_params."""
+    _fields_ = [("levels", c_int), ("range", c_int), ("penalty", c_int)]
+
+
+ALL_REDUCE_FN =ctypes.CFUNCTYPE(c_int, c_void_p, c_void_p, c_size_t, c_void_p)          # (user, buf, count, stream)
 BROADCAST_FN = ctypes.CFUNCTYPE(c_int, c_void_p, c_void_p, c_size_t, c_int, c_void_p)    # (user, buf, bytes, root, stream)
 SENDRECV_FN = ctypes.CFUNCTYPE(c_int, c_void_p, POINTER(WctP2P), c_int, c_void_p)        # (user, ops, n_ops, stream)
 
@@ -231,6 +241,12 @@ def load() -> ctypes.CDLL:
     lib.wct_moments_track.argtypes = [c_void_p, c_void_p, c_int, c_int, vp, vp]
     lib.wct_temporal_blend.argtypes = [c_void_p, vp, c_int, c_int, vp, vp, vp, c_int, c_int, c_float, c_float, c_int, vp, vp, vp, c_int]
     lib.wct_stylize_clip.argtypes = [c_void_p, c_void_p, vp, c_int, c_int, c_float, vp, vp, c_int, ip, ip]
+    lib.wct_motion_shape.argtypes = [c_int, c_int, ip, ip]
+    lib.wct_motion_luma.argtypes = [c_void_p, vp, c_int, c_int, c_int, c_int, c_int, vp]
+    lib.wct_motion_estimate.argtypes = [c_void_p, vp, c_int, c_int, vp, c_int, c_int, POINTER(WctMotionParams), vp]
+    lib.wct_motion_blend.argtypes = [c_void_p, vp, c_int, c_int, vp, vp, vp, c_int, c_int, c_float, c_float, c_int, vp, vp, vp, c_int, vp]
+    lib.wct_motion_attach.argtypes = [c_void_p, c_void_p, POINTER(WctMotionParams)]
+    lib.wct_motion_export.argtypes = [c_void_p, c_void_p, vp]
     lib.wct_set_transform.argtypes = [c_void_p, c_int]
     lib.wct_get_transform.argtypes = [c_void_p, ip]
     lib.wct_transform_solve.argtypes = [c_void_p, c_int, c_int, c_double, vp, vp, vp, c_double, vp, vp, ip]

@@ -18,7 +18,7 @@ import ctypes
 import logging
 import os
 from ctypes import c_size_t, byref, c_int, c_void_p
-from typing import Dict, List, Optional
+from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 import torch
@@ -1112,11 +1112,91 @@ class WCT:
 
     # ------------------------------------------------------------------ video mode (include/wct_hip_video.h)
     def clip(self, H: int, W: int, rate: float = _lib.CLIP_RATE, cut: float = _lib.CLIP_CUT, blend: float = _lib.CLIP_BLEND,
-             sigma: float = _lib.CLIP_SIGMA, radius: int = _lib.CLIP_RADIUS) -> "Clip":
+             sigma: float = _lib.CLIP_SIGMA, radius: int = _lib.CLIP_RADIUS, motion=None) -> "Clip":
         """The state of one sequence of H x W frames (wct_clip_create): content statistics tracked over time at `rate` with a
         scene-cut reset above the distance `cut`, and a recursive blend of the output with weight `blend` where the content did not
-        move (`sigma`, `radius`).  Allocates everything once; frames then go through Clip.stylize()."""
-        return Clip(self, int(H), int(W), float(rate), float(cut), float(blend), float(sigma), int(radius))
+        move (`sigma`, `radius`).  Allocates everything once; frames then go through Clip.stylize().  motion: None -- the blend
+        compares the frames pixel by pixel; True or a dict of levels / range / penalty -- against the previous frame displaced by a
+        block-matched field (Clip.attach_motion; include/wct_hip_motion.h)."""
+        c = Clip(self, int(H), int(W), float(rate), float(cut), float(blend), float(sigma), int(radius))
+        if motion is not None and motion is not False:
+            try:
+                c.attach_motion(**({} if motion is True else dict(motion)))
+            except Exception:
+                c.close()
+                raise
+        return c
+
+    # ------------------------------------------------------------------ motion compensation (include/wct_hip_motion.h)
+    @staticmethod
+    def motion_shape(Ho: int, Wo: int) -> Tuple[int, int]:
+        """The 8 x 8 block grid (nby, nbx) of an Ho x Wo image (wct_motion_shape)."""
+        nby, nbx = c_int(), c_int()
+        if _lib.load().wct_motion_shape(int(Ho), int(Wo), byref(nby), byref(nbx)) != _lib.WCT_OK:
+            raise ValueError("libwct_hip: wct_motion_shape: a non-empty image expected, got %dx%d" % (Ho, Wo))
+        return nby.value, nbx.value
+
+    def _window(self, c: torch.Tensor, Ho: Optional[int], Wo: Optional[int]) -> Tuple[int, int]:
+        return (int(c.shape[1]) if Ho is None else int(Ho)), (int(c.shape[2]) if Wo is None else int(Wo))
+
+    @torch.no_grad()
+    def motion_luma(self, img: torch.Tensor, levels: int = _lib.MOTION_LEVELS, Ho: Optional[int] = None, Wo: Optional[int] = None):
+        """The uint8 luma pyramid of the top-left Ho x Wo (default: all) of a [1,3,H,W] / [3,H,W] image (wct_motion_luma): a list of
+        `levels` uint8 [H_k, W_k] device tensors, level 0 first."""
+        c = self._img(img)
+        Ho, Wo = self._window(c, Ho, Wo)
+        levels = int(levels)
+        shapes = [(Ho >> k, Wo >> k) for k in range(max(levels, 0))]
+        out = torch.empty(max(sum(h * w for h, w in shapes), 1), device=c.device, dtype=torch.uint8)
+        self._stream()
+        self._chk(self._lib.wct_motion_luma(self._ctx, c.data_ptr(), int(c.shape[1]), int(c.shape[2]), Ho, Wo, levels, out.data_ptr()))
+        res, at = [], 0
+        for h, w in shapes:
+            res.append(out[at:at + h * w].view(h, w))
+            at += h * w
+        return res
+
+    @torch.no_grad()
+    def motion_estimate(self, content: torch.Tensor, prev_content: torch.Tensor, levels: int = _lib.MOTION_LEVELS, range: int = _lib.MOTION_RANGE,
+                        penalty: int = _lib.MOTION_PENALTY, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The block-matched field between the top-left Ho x Wo of `content` and `prev_content` ([1,3,Ho,Wo]) (wct_motion_estimate):
+        int16 [nby, nbx, 2] = (vy, vx) per 8 x 8 block, content(y, x) ~ prev_content(y + vy, x + vx)."""
+        c, q = self._img(content), self._img(prev_content)
+        Ho, Wo = int(q.shape[1]), int(q.shape[2])
+        nby, nbx = (Ho + 7) // 8, (Wo + 7) // 8
+        out = self._out_like(out, "motion_estimate", nby * nbx * 2, torch.int16)
+        if out is None:
+            out = torch.empty((nby, nbx, 2), device=c.device, dtype=torch.int16)
+        p = _lib.WctMotionParams(int(levels), int(range), int(penalty))
+        self._stream()
+        self._chk(self._lib.wct_motion_estimate(self._ctx, c.data_ptr(), int(c.shape[1]), int(c.shape[2]), q.data_ptr(), Ho, Wo, byref(p), out.data_ptr()))
+        return out.view(nby, nbx, 2)
+
+    @torch.no_grad()
+    def motion_blend(self, content: torch.Tensor, prev_content: torch.Tensor, stylised: torch.Tensor, prev_out: torch.Tensor,
+                     mv: Optional[torch.Tensor], blend: float = _lib.CLIP_BLEND, sigma: float = _lib.CLIP_SIGMA, radius: int = _lib.CLIP_RADIUS,
+                     cut_flag: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, u8: bool = False, round_mode: int = 0):
+        """temporal_blend against prev_content and prev_out displaced by the field `mv` (int16 [nby, nbx, 2]; None: the zero
+        field) (wct_motion_blend).  Returns what temporal_blend returns."""
+        c, q, s, p = self._img(content), self._img(prev_content), self._img(stylised), self._img(prev_out)
+        Hc, Wc, Ho, Wo = int(c.shape[1]), int(c.shape[2]), int(s.shape[1]), int(s.shape[2])
+        if tuple(q.shape) != (3, Ho, Wo) or tuple(p.shape) != (3, Ho, Wo):
+            raise ValueError("motion_blend: prev_content %s and prev_out %s must have the stylised image's shape %s"
+                             % (tuple(q.shape), tuple(p.shape), tuple(s.shape)))
+        if cut_flag is not None and (cut_flag.dtype != torch.int32 or not cut_flag.is_cuda or cut_flag.numel() != 1):
+            raise ValueError("motion_blend: cut_flag must be an int32 device tensor with one value")
+        if mv is not None:
+            mv = self._out_like(mv, "motion_blend: mv", ((Ho + 7) // 8) * ((Wo + 7) // 8) * 2, torch.int16)
+        out = self._out_like(out, "motion_blend", 3 * Ho * Wo)
+        if out is None:
+            out = torch.empty((1, 3, Ho, Wo), device=s.device, dtype=torch.float32)
+        hwc = torch.empty((Ho, Wo, 3), device=s.device, dtype=torch.uint8) if u8 else None
+        self._stream()
+        self._chk(self._lib.wct_motion_blend(self._ctx, c.data_ptr(), Hc, Wc, q.data_ptr(), s.data_ptr(), p.data_ptr(), Ho, Wo, float(blend),
+                                             float(sigma), int(radius), cut_flag.data_ptr() if cut_flag is not None else None, out.data_ptr(),
+                                             hwc.data_ptr() if u8 else None, int(round_mode), mv.data_ptr() if mv is not None else None))
+        out = out.view(1, 3, Ho, Wo)
+        return (out, hwc) if u8 else out
 
     @torch.no_grad()
     def moments_track(self, clip: "Clip", level: int, sum_c: torch.Tensor, sumsq_c: torch.Tensor, decide: bool = False):
@@ -1489,6 +1569,7 @@ class Clip:
         self._clip = c_void_p()
         owner._chk(owner._lib.wct_clip_create(owner._ctx, H, W, byref(self.params), byref(self._clip)))
         self.Ho, self.Wo = H // 16 * 16, W // 16 * 16
+        self.motion = None                # attach_motion: the parameters of the attached motion compensation
 
     def _handle(self) -> c_void_p:
         if not self._clip.value:
@@ -1518,6 +1599,33 @@ class Clip:
                                        int(round_mode), byref(ho), byref(wo)))
         out = out.view(1, 3, self.Ho, self.Wo)
         return (out, hwc) if u8 else out
+
+    def attach_motion(self, levels: int = _lib.MOTION_LEVELS, range: int = _lib.MOTION_RANGE, penalty: int = _lib.MOTION_PENALTY) -> None:
+        """Motion compensation for the frames from now on (wct_motion_attach): allocates the clip's motion block once; the next frame
+        is a first frame."""
+        o = self.owner
+        p = _lib.WctMotionParams(int(levels), int(range), int(penalty))
+        o._stream()
+        o._chk(o._lib.wct_motion_attach(o._ctx, self._handle(), byref(p)))
+        self.motion = {"levels": int(levels), "range": int(range), "penalty": int(penalty)}
+
+    def detach_motion(self) -> None:
+        """Video mode without motion compensation again (wct_motion_attach with NULL); the next frame is a first frame."""
+        o = self.owner
+        o._stream()
+        o._chk(o._lib.wct_motion_attach(o._ctx, self._handle(), None))
+        self.motion = None
+
+    @torch.no_grad()
+    def motion_field(self) -> torch.Tensor:
+        """The last frame's field, int16 [nby, nbx, 2] = (vy, vx) per 8 x 8 block, as a device tensor in stream order
+        (wct_motion_export); all zero after a cut."""
+        o = self.owner
+        nby, nbx = (self.Ho + 7) // 8, (self.Wo + 7) // 8
+        mv = torch.empty((nby, nbx, 2), device=o.stats_device, dtype=torch.int16)
+        o._stream()
+        o._chk(o._lib.wct_motion_export(o._ctx, self._handle(), mv.data_ptr()))
+        return mv
 
     def reset(self) -> None:
         """The next frame is a first frame: tracked statistics and the previous output are not used (asynchronous)."""
