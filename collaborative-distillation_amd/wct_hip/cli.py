@@ -57,6 +57,7 @@ is no CPU fallback.
 from __future__ import annotations
 
 import argparse
+import collections
 import math
 import os
 import sys
@@ -301,45 +302,34 @@ def region_out_name(args, content_file: str) -> str:
     return out_name(args, content_file.split(".")[0] + "+regions.jpg")
 
 
-def run_regions(args, wct, content_dir, logprinter) -> float:
-    """--maskPath: one stylisation per content, region k against --region_styles[k] (wct_stylize_regions); the serial loop."""
-    import torch
-    from PIL import Image
-    jobs = region_jobs(content_dir, args.maskPath, args.picked_content_mark)
+def run_regions(args, wct, jobs, content_dir, style_dir, logprinter) -> Tuple[float, int]:
+    """--maskPath: one stylisation per content of region_jobs(), region k against --region_styles[k] (wct_stylize_regions); the serial
+    loop.  Returns (total seconds, contents)."""
     styles = [p for p in args.region_styles.split(",") if p]
-    s_dev = [_to_tensor(wct, torch.from_numpy(load_rgb_u8(p)).cuda(), args.style_size) for p in styles]
+
+    def convert():
+        return [_to_tensor(wct, _upload_u8(p), args.style_size) for p in styles]
+
+    s_dev = convert()       # once per run, outside every job's timer
     # --styleMaskPath: the styles' own label maps, at each style's size after --style_size (wct_stylize_guided); none -> wct_stylize_regions
     smask = [style_mask_path(getattr(args, "styleMaskPath", None), p) for p in styles]
-    s_lab = [torch.from_numpy(load_mask(m, (int(t.shape[-2]), int(t.shape[-1])))).cuda() if m else None for m, t in zip(smask, s_dev)]
+    s_lab = [_on_device(load_mask(m, (int(t.shape[-2]), int(t.shape[-1])))) if m else None for m, t in zip(smask, s_dev)]
     guided = any(m is not None for m in s_lab)
 
-    def stylise(c_f32, st, lab):
-        if guided:
-            return wct.stylize_guided(c_f32, st, lab, s_lab, None, args.alpha, args.num_run)
-        return wct.stylize_regions(c_f32, st, lab, args.alpha, args.num_run)
+    def label_map(mpath):
+        return lambda c_u8: _on_device(load_mask(mpath, resized_shape(int(c_u8.shape[0]), int(c_u8.shape[1]), args.content_size)))
 
-    avg = 0.0
-    for i, (cfile, mpath) in enumerate(jobs):
-        logprinter("\n" + "*" * 30 + ' #%s: Transferring "%s" by regions (%s)' % (i, cfile, mpath))
-        c_u8 = torch.from_numpy(load_rgb_u8(os.path.join(content_dir, cfile))).pin_memory().cuda(non_blocking=True)
-        H, W = resized_shape(int(c_u8.shape[0]), int(c_u8.shape[1]), args.content_size)
-        lab = torch.from_numpy(load_mask(mpath, (H, W))).cuda()
-        t0 = time.time()
-        c_f32 = _to_tensor(wct, c_u8, args.content_size)
-        res = stylise(c_f32, s_dev, lab)
-        if wct.saturation_count(reset=True):
-            logprinter("WARNING: f16x3 range exceeded for this content -> recomputing it with exact-fp32 convolutions")
-            wct.set_conv_mode("fp32")
-            s32 = [_to_tensor(wct, torch.from_numpy(load_rgb_u8(p)).cuda(), args.style_size) for p in styles]
-            res = stylise(c_f32, s32, lab)
-            wct.sync()
-            wct.set_conv_mode("f16x3")
-        out = _finish_u8(wct, args, res, c_f32).cpu().numpy()
-        Image.fromarray(out).save(region_out_name(args, cfile))
-        dt = time.time() - t0
-        avg += dt
-        logprinter("Elapsed time is: %.4f seconds" % dt)
-    return avg
+    def stylise(c_f32, lab):
+        def once(fresh):
+            st = convert() if fresh else s_dev      # the recompute reads and converts the styles again
+            if guided:
+                return wct.stylize_guided(c_f32, st, lab, s_lab, None, args.alpha, args.num_run)
+            return wct.stylize_regions(c_f32, st, lab, args.alpha, args.num_run)
+        return _recompute_fp32(wct, logprinter, "content", once)
+
+    return _run_jobs(args, wct, logprinter, [
+        Job(' #%s: Transferring "%s" by regions (%s)' % (i, cfile, mpath), os.path.join(content_dir, cfile), label_map(mpath), stylise,
+            region_out_name(args, cfile)) for i, (cfile, mpath) in enumerate(jobs)]), len(jobs)
 
 
 def check_region_args(args) -> None:
@@ -381,39 +371,24 @@ def check_auto_args(args) -> None:
     args.auto_iters = 10 if iters is None else iters
 
 
-def run_auto(args, wct, pairs, content_dir, style_dir, logprinter) -> float:
+def run_auto(args, wct, pairs, content_dir, style_dir, logprinter) -> Tuple[float, int]:
     """--auto_regions: per pair, k-means label maps from the features of --auto_level (wct_feature_regions), then the region-to-region
-    cascade against the one style (wct_stylize_guided); one pair at a time; returns the summed per-pair time."""
-    import torch
-    from PIL import Image
+    cascade against the one style (wct_stylize_guided); one pair at a time.  Returns (total seconds, pairs)."""
     K = args.auto_regions
-    avg = 0.0
-    for i, (cfile, sfile) in enumerate(pairs):
-        imname = pair_name(cfile, sfile)
-        logprinter("\n" + "*" * 30 + ' #%s: Transferring "%s" (%d feature regions of level %d, %d iterations)' % (i, imname, K, args.auto_level, args.auto_iters))
-        c_u8 = torch.from_numpy(load_rgb_u8(os.path.join(content_dir, cfile))).pin_memory().cuda(non_blocking=True)
-        s_u8 = torch.from_numpy(load_rgb_u8(os.path.join(style_dir, sfile))).pin_memory().cuda(non_blocking=True)
-        t0 = time.time()
-        c_f32 = _to_tensor(wct, c_u8, args.content_size)
 
-        def once():
+    def stylise(c_f32, s_u8):
+        def once(fresh):        # every pass converts the style and clusters again
             s_f32 = _to_tensor(wct, s_u8, args.style_size)
             lab_c, lab_s = wct.feature_regions(c_f32, s_f32, K, args.auto_level, args.auto_iters)
             return wct.stylize_guided(c_f32, [s_f32], lab_c, [lab_s], [0] * K, args.alpha, args.num_run)
+        return _recompute_fp32(wct, logprinter, "pair", once)
 
-        res = once()
-        if wct.saturation_count(reset=True):
-            logprinter("WARNING: f16x3 range exceeded for this pair -> recomputing it with exact-fp32 convolutions")
-            wct.set_conv_mode("fp32")
-            res = once()
-            wct.sync()
-            wct.set_conv_mode("f16x3")
-        out = _finish_u8(wct, args, res, c_f32).cpu().numpy()
-        Image.fromarray(out).save(out_name(args, imname))
-        dt = time.time() - t0
-        avg += dt
-        logprinter("Elapsed time is: %.4f seconds" % dt)
-    return avg
+    def job(i, cfile, sfile):
+        imname = pair_name(cfile, sfile)
+        return Job(' #%s: Transferring "%s" (%d feature regions of level %d, %d iterations)' % (i, imname, K, args.auto_level, args.auto_iters),
+                   os.path.join(content_dir, cfile), lambda c_u8: _upload_u8(os.path.join(style_dir, sfile)), stylise, out_name(args, imname))
+
+    return _run_jobs(args, wct, logprinter, [job(i, c, s) for i, (c, s) in enumerate(pairs)]), len(pairs)
 
 
 def check_color_args(args) -> None:
@@ -493,47 +468,34 @@ def _swap_pair(wct, args, logprinter, c_f32, style_f32):
     """One pair of --swap_level: wct_stylize_swap, and after a clamp of the f16x3 range the same call under the exact-fp32 convolutions
     (`style_f32()` makes the style tensor afresh for it).  The patch match stays f16x3 in that recompute -- whitened features are O(1) --
     so a clamp inside it is not cured: it still counts, is reported in the log, and the pair's result is returned all the same."""
-    res = wct.stylize_swap(c_f32, style_f32(), args.swap_level, args.swap_match, args.alpha, args.num_run)
-    if wct.saturation_count(reset=True):
-        logprinter("WARNING: f16x3 range exceeded for this pair -> recomputing it with exact-fp32 convolutions")
-        wct.set_conv_mode("fp32")
-        try:
-            res = wct.stylize_swap(c_f32, style_f32(), args.swap_level, args.swap_match, args.alpha, args.num_run)
-        finally:
-            wct.set_conv_mode("f16x3")
-        # no wct.sync() here: it raises on a clamp; saturation_count synchronises, counts and acknowledges it instead
-        if wct.saturation_count(reset=True):
-            logprinter("WARNING: a feature of this pair left the f16 range inside the patch match and was clamped there; the chosen "
-                       "patches may deviate")
+    passes = []
+
+    def once(fresh):
+        passes.append(fresh)
+        return wct.stylize_swap(c_f32, style_f32(), args.swap_level, args.swap_match, args.alpha, args.num_run)
+
+    # no wct.sync() in the recompute: it raises on a clamp; saturation_count synchronises, counts and acknowledges it instead
+    res = _recompute_fp32(wct, logprinter, "pair", once, sync=False)
+    if passes[-1] and wct.saturation_count(reset=True):
+        logprinter("WARNING: a feature of this pair left the f16 range inside the patch match and was clamped there; the chosen "
+                   "patches may deviate")
     return res
 
 
-def run_swap(args, wct, pairs, content_dir, style_dir, logprinter) -> float:
+def run_swap(args, wct, pairs, content_dir, style_dir, logprinter) -> Tuple[float, int]:
     """--swap_level: the reference's loop with the cascade of wct_stylize_swap, one pair at a time (the swapped level needs the style's
-    feature map itself, so there are no style statistics to cache); returns the summed per-pair time."""
-    import torch
-    from PIL import Image
-    avg = 0.0
-    style_dev = {}
-    for i, (cfile, sfile) in enumerate(pairs):
+    feature map itself, so there are no style statistics to cache).  Returns (total seconds, pairs)."""
+    on_device = _device_images(8)
+
+    def stylise(c_f32, s_u8):
+        return _swap_pair(wct, args, logprinter, c_f32, lambda: _to_tensor(wct, s_u8, args.style_size))
+
+    def job(i, cfile, sfile):
         imname = pair_name(cfile, sfile)
-        logprinter("\n" + "*" * 30 + ' #%s: Transferring "%s" (patch swap at level %d, %s)' % (i, imname, args.swap_level, args.swap_match))
-        c_u8 = torch.from_numpy(load_rgb_u8(os.path.join(content_dir, cfile))).pin_memory().cuda(non_blocking=True)
-        s_u8 = style_dev.get(sfile)
-        if s_u8 is None:
-            s_u8 = torch.from_numpy(load_rgb_u8(os.path.join(style_dir, sfile))).pin_memory().cuda(non_blocking=True)
-            style_dev[sfile] = s_u8
-            while len(style_dev) > 8:
-                style_dev.pop(next(iter(style_dev)))
-        t0 = time.time()
-        c_f32 = _to_tensor(wct, c_u8, args.content_size)
-        res = _swap_pair(wct, args, logprinter, c_f32, lambda: _to_tensor(wct, s_u8, args.style_size))
-        out = _finish_u8(wct, args, res, c_f32).cpu().numpy()   # .cpu() syncs
-        Image.fromarray(out).save(out_name(args, imname))
-        dt = time.time() - t0
-        avg += dt
-        logprinter("Elapsed time is: %.4f seconds" % dt)
-    return avg
+        return Job(' #%s: Transferring "%s" (patch swap at level %d, %s)' % (i, imname, args.swap_level, args.swap_match),
+                   os.path.join(content_dir, cfile), lambda c_u8: on_device(os.path.join(style_dir, sfile)), stylise, out_name(args, imname))
+
+    return _run_jobs(args, wct, logprinter, [job(i, c, s) for i, (c, s) in enumerate(pairs)]), len(pairs)
 
 
 def level_scale_list(text: str) -> Tuple[int, ...]:
@@ -598,51 +560,27 @@ def _scale_once(wct, args, c_f32, style, coarse):
 def _scale_pair(wct, args, logprinter, c_f32, style_f32, coarse_f32):
     """One pair of --level_scale, and after a clamp of the f16x3 range the same under the exact-fp32 convolutions (`style_f32()` and
     `coarse_f32()` make the style tensors afresh for it; the resampler and the merge are fp32 and clamp nothing)."""
-    res = _scale_once(wct, args, c_f32, style_f32(), coarse_f32())
-    if wct.saturation_count(reset=True):
-        logprinter("WARNING: f16x3 range exceeded for this pair -> recomputing it with exact-fp32 convolutions")
-        wct.set_conv_mode("fp32")
-        try:
-            res = _scale_once(wct, args, c_f32, style_f32(), coarse_f32())
-            wct.sync()
-        finally:
-            wct.set_conv_mode("f16x3")
-    return res
+    return _recompute_fp32(wct, logprinter, "pair", lambda fresh: _scale_once(wct, args, c_f32, style_f32(), coarse_f32()))
 
 
-def run_scale(args, wct, pairs, content_dir, style_dir, logprinter) -> float:
-    """--level_scale: the reference's loop with the cascade of wct_stylize_scaled, one pair at a time; returns the summed per-pair time."""
-    import torch
-    from PIL import Image
-    avg = 0.0
-    style_dev = {}
+def run_scale(args, wct, pairs, content_dir, style_dir, logprinter) -> Tuple[float, int]:
+    """--level_scale: the reference's loop with the cascade of wct_stylize_scaled, one pair at a time.  Returns (total seconds, pairs)."""
+    on_device = _device_images(8)
 
-    def on_device(path):
-        u8 = style_dev.get(path)
-        if u8 is None:
-            u8 = torch.from_numpy(load_rgb_u8(path)).pin_memory().cuda(non_blocking=True)
-            style_dev[path] = u8
-            while len(style_dev) > 8:
-                style_dev.pop(next(iter(style_dev)))
-        return u8
+    def stylise(c_f32, u8):
+        s_u8, k_u8 = u8
+        return _scale_pair(wct, args, logprinter, c_f32, lambda: _to_tensor(wct, s_u8, args.style_size),
+                           lambda: _to_tensor(wct, k_u8, args.style_size) if k_u8 is not None else None)
 
-    for i, (cfile, sfile) in enumerate(pairs):
+    def job(i, cfile, sfile):
         imname = pair_name(cfile, sfile)
-        logprinter("\n" + "*" * 30 + ' #%s: Transferring "%s" (level divisors %s, detail %g%s)' % (
-            i, imname, args.level_scale, args.scale_detail, ", coarse style %s" % args.coarse_style if args.coarse_style else ""))
-        c_u8 = torch.from_numpy(load_rgb_u8(os.path.join(content_dir, cfile))).pin_memory().cuda(non_blocking=True)
-        s_u8 = on_device(os.path.join(style_dir, sfile))
-        k_u8 = on_device(args.coarse_style) if args.coarse_style else None
-        t0 = time.time()
-        c_f32 = _to_tensor(wct, c_u8, args.content_size)
-        res = _scale_pair(wct, args, logprinter, c_f32, lambda: _to_tensor(wct, s_u8, args.style_size),
-                          lambda: _to_tensor(wct, k_u8, args.style_size) if k_u8 is not None else None)
-        out = _finish_u8(wct, args, res, c_f32).cpu().numpy()   # .cpu() syncs
-        Image.fromarray(out).save(out_name(args, imname))
-        dt = time.time() - t0
-        avg += dt
-        logprinter("Elapsed time is: %.4f seconds" % dt)
-    return avg
+        return Job(' #%s: Transferring "%s" (level divisors %s, detail %g%s)' % (
+                       i, imname, args.level_scale, args.scale_detail, ", coarse style %s" % args.coarse_style if args.coarse_style else ""),
+                   os.path.join(content_dir, cfile),
+                   lambda c_u8: (on_device(os.path.join(style_dir, sfile)), on_device(args.coarse_style) if args.coarse_style else None),
+                   stylise, out_name(args, imname))
+
+    return _run_jobs(args, wct, logprinter, [job(i, c, s) for i, (c, s) in enumerate(pairs)]), len(pairs)
 
 
 VIDEO_FLAGS = (("temporal_rate", "--temporal_rate"), ("scene_cut", "--scene_cut"), ("temporal_blend", "--temporal_blend"),
@@ -726,14 +664,17 @@ def check_motion_args(args) -> None:
         raise ValueError("--motion_penalty: 0 .. 255 expected, got %r" % (args.motion_penalty,))
 
 
-def run_video(args, wct, content_dir, style_dir, logprinter) -> Tuple[float, int]:
+def video_jobs(args, content_dir, style_dir) -> Tuple[List[str], List[str]]:
+    """(frames, styles) of --video, both sorted by name."""
+    return (video_frames(content_dir, args.picked_content_mark),
+            sorted(x for x in os.listdir(style_dir) if is_image_file(x) and args.picked_style_mark in x))
+
+
+def run_video(args, wct, jobs, content_dir, style_dir, logprinter) -> Tuple[float, int]:
     """--video: per style one clip -- the style prepared once, then the frames in name order through wct_stylize_clip, one at a time;
-    one image per (frame, style) under the usual name.  Returns (summed per-frame time, frames written)."""
-    import torch
+    one image per (frame, style) of video_jobs() under the usual name.  Returns (summed per-frame time, frames written)."""
     from PIL import Image
-    frames = video_frames(content_dir, args.picked_content_mark)
-    styles = sorted(x for x in os.listdir(style_dir) if is_image_file(x) and args.picked_style_mark in x)
-    logprinter("Number of frames: %s, styles: %s" % (len(frames), len(styles)))
+    frames, styles = jobs
     if not frames or not styles:
         return 0.0, 0
     shapes = []
@@ -747,15 +688,14 @@ def run_video(args, wct, content_dir, style_dir, logprinter) -> Tuple[float, int
     H, W = shapes[0][1]
     avg, n = 0.0, 0
     for sfile in styles:
-        s_u8 = torch.from_numpy(load_rgb_u8(os.path.join(style_dir, sfile))).pin_memory().cuda(non_blocking=True)
-        wct.style_prepare(_to_tensor(wct, s_u8, args.style_size))
-        clip = wct.clip(H, W, args.temporal_rate, args.scene_cut, args.temporal_blend, args.temporal_sigma, args.temporal_radius, motion=motion)
+        wct.style_prepare(_to_tensor(wct, _upload_u8(os.path.join(style_dir, sfile)), args.style_size))
+        clip =wct.clip(H, W, args.temporal_rate, args.scene_cut, args.temporal_blend, args.temporal_sigma, args.temporal_radius, motion=motion)
         try:
             for i, cfile in enumerate(frames):
                 imname = pair_name(cfile, sfile)
                 logprinter("\n" + "*" * 30 + ' #%s: Transferring "%s" (video: rate %g, cut %g, blend %g%s)' % (
                     i, imname, args.temporal_rate, args.scene_cut, args.temporal_blend, motion_note))
-                c_u8 = torch.from_numpy(load_rgb_u8(os.path.join(content_dir, cfile))).pin_memory().cuda(non_blocking=True)
+                c_u8 = _upload_u8(os.path.join(content_dir, cfile))
                 t0 = time.time()
                 c_f32 = _to_tensor(wct, c_u8, args.content_size)
                 _, hwc = clip.stylize(c_f32, args.alpha, u8=True, round_mode=args.round_mode)
@@ -862,50 +802,39 @@ def interp_out_name(args, content_file: str, blend: bool = False) -> str:
     return out_name(args, content_file.split(".")[0] + ("+blend.jpg" if blend else "+interp.jpg"))
 
 
-def run_interp(args, wct, content_dir, logprinter) -> Tuple[float, int]:
-    """--interp_styles: one stylisation per content against the blend of the styles (wct_stylize_interp) or, with --weightPath, with
-    per-pixel weights (wct_stylize_blend); the serial loop.  Returns (total seconds, contents)."""
-    import torch
-    from PIL import Image
+def interp_jobs(args, content_dir, style_dir)-> List[Tuple[str, Optional[List[str]]]]:
+    """--interp_styles: every picked content (listdir order), with its weight maps under --weightPath (weight_jobs) or None."""
+    if args.weightPath is not None:
+        return weight_jobs(content_dir, args.weightPath, len(interp_style_list(args)), args.picked_content_mark)
+    return [(c, None) for c in os.listdir(content_dir) if is_image_file(c) and args.picked_content_mark in c]
+
+
+def run_interp(args, wct, jobs, content_dir, style_dir, logprinter) -> Tuple[float, int]:
+    """--interp_styles: one stylisation per content of interp_jobs() against the blend of the styles (wct_stylize_interp) or, with
+    --weightPath, with per-pixel weights (wct_stylize_blend); the serial loop.  Returns (total seconds, contents)."""
     styles = interp_style_list(args)
-    s_dev = [_to_tensor(wct, torch.from_numpy(load_rgb_u8(p)).cuda(), args.style_size) for p in styles]
+
+    def convert():
+        return [_to_tensor(wct, _upload_u8(p), args.style_size) for p in styles]
+
+    s_dev = convert()       # once per run, outside every job's timer
     blend = args.weightPath is not None
-    if blend:
-        jobs = weight_jobs(content_dir, args.weightPath, len(styles), args.picked_content_mark)
-    else:
-        jobs = [(c, None) for c in os.listdir(content_dir) if is_image_file(c) and args.picked_content_mark in c]
-        lam = interp_weight_list(args)
-    logprinter("Number of contents: %s" % len(jobs))
+    lam = None if blend else interp_weight_list(args)
 
-    def run(c_f32, st, wmap):
-        if blend:
-            return wct.stylize_blend(c_f32, st, wmap, args.alpha, args.num_run)
-        return wct.stylize_interp(c_f32, st, lam, args.alpha, args.num_run)
+    def weight_maps(wpaths):
+        return lambda c_u8: _on_device(load_weights(wpaths, resized_shape(int(c_u8.shape[0]), int(c_u8.shape[1]), args.content_size)))
 
-    avg = 0.0
-    for i, (cfile, wpaths) in enumerate(jobs):
-        logprinter("\n" + "*" * 30 + ' #%s: Transferring "%s" by %s' % (i, cfile, "weight maps" if blend else "interpolation"))
-        c_u8 = torch.from_numpy(load_rgb_u8(os.path.join(content_dir, cfile))).pin_memory().cuda(non_blocking=True)
-        wmap = None
-        if blend:
-            H, W = resized_shape(int(c_u8.shape[0]), int(c_u8.shape[1]), args.content_size)
-            wmap = torch.from_numpy(load_weights(wpaths, (H, W))).cuda()
-        t0 = time.time()
-        c_f32 = _to_tensor(wct, c_u8, args.content_size)
-        res = run(c_f32, s_dev, wmap)
-        if wct.saturation_count(reset=True):
-            logprinter("WARNING: f16x3 range exceeded for this content -> recomputing it with exact-fp32 convolutions")
-            wct.set_conv_mode("fp32")
-            s32 = [_to_tensor(wct, torch.from_numpy(load_rgb_u8(p)).cuda(), args.style_size) for p in styles]
-            res = run(c_f32, s32, wmap)
-            wct.sync()
-            wct.set_conv_mode("f16x3")
-        out = _finish_u8(wct, args, res, c_f32).cpu().numpy()
-        Image.fromarray(out).save(interp_out_name(args, cfile, blend))
-        dt = time.time() - t0
-        avg += dt
-        logprinter("Elapsed time is: %.4f seconds" % dt)
-    return avg, len(jobs)
+    def stylise(c_f32, wmap):
+        def once(fresh):
+            st = convert() if fresh else s_dev      # the recompute reads and converts the styles again
+            if blend:
+                return wct.stylize_blend(c_f32, st, wmap, args.alpha, args.num_run)
+            return wct.stylize_interp(c_f32, st, lam, args.alpha, args.num_run)
+        return _recompute_fp32(wct, logprinter, "content", once)
+
+    return _run_jobs(args, wct, logprinter, [
+        Job(' #%s: Transferring "%s" by %s' % (i, cfile, "weight maps" if blend else "interpolation"), os.path.join(content_dir, cfile),
+            weight_maps(wpaths) if blend else None, stylise, interp_out_name(args, cfile, blend)) for i, (cfile, wpaths) in enumerate(jobs)]), len(jobs)
 
 
 def synthesis_shape(H: int, W: int, size: int) -> Tuple[int, int]:
@@ -969,43 +898,29 @@ def check_synthesis_args(args) -> None:
         synthesis_size(args.synthesis_size)
 
 
-def run_synthesis(args, wct, logprinter) -> Tuple[float, int]:
-    """--synthesis: one image per texture of --texturePath (wct_synthesize: noise of --seed and stream id = the texture's index as the
-    content, the texture as the style); the serial loop.  Returns (total seconds, textures)."""
-    import torch
-    from PIL import Image
-    jobs = texture_jobs(args.texturePath)
-    logprinter("Number of content-style pairs: %s" % len(jobs))
+def run_synthesis(args, wct, jobs, content_dir, style_dir, logprinter) -> Tuple[float, int]:
+    """--synthesis: one image per texture of texture_jobs() (wct_synthesize: noise of --seed and stream id = the texture's index as
+    the content, the texture as the style); the serial loop.  There is no content: the job's pre-timer step uploads the texture, and
+    _finish_u8 is the plain uint8 conversion (--preserve_color and --smooth_radius are refused).  Returns (total seconds, textures)."""
     size = synthesis_size(args.synthesis_size) if args.synthesis_size is not None else None
-    avg = 0.0
-    for i, tfile in enumerate(jobs):
-        imname = tfile.split(".")[0] + ".jpg"
-        logprinter("\n" + "*" * 30 + ' #%s: Transferring "%s"' % (i, imname))
-        t_u8 = torch.from_numpy(load_rgb_u8(os.path.join(args.texturePath, tfile))).pin_memory().cuda(non_blocking=True)
-        t0 = time.time()
-        if args.style_size:
-            t_f32 = wct.resize_u8(t_u8, synthesis_shape(int(t_u8.shape[0]), int(t_u8.shape[1]), args.style_size), to_tensor=True, filter="bicubic")
-        else:
-            t_f32 = wct.to_tensor_u8(t_u8)
-        if size is not None:
-            H, W = synthesis_noise_shape(*size)
-        else:
-            H, W = int(t_f32.shape[2]), int(t_f32.shape[3])
-        res = wct.synthesize(t_f32, H, W, seed=args.seed, stream_id=i, alpha=args.alpha, num_run=args.num_run)
-        if wct.saturation_count(reset=True):
-            logprinter("WARNING: f16x3 range exceeded for this texture -> recomputing it with exact-fp32 convolutions")
-            wct.set_conv_mode("fp32")
-            res = wct.synthesize(t_f32, H, W, seed=args.seed, stream_id=i, alpha=args.alpha, num_run=args.num_run)
-            wct.sync()
-            wct.set_conv_mode("f16x3")
-        if size is not None:
-            res = res[:, :, :size[0], :size[1]]
-        out = wct.to_u8(res, args.round_mode).cpu().numpy()
-        Image.fromarray(out).save(synthesis_out_name(args, tfile))
-        dt = time.time() - t0
-        avg += dt
-        logprinter("Elapsed time is: %.4f seconds" % dt)
-    return avg, len(jobs)
+
+    def job(i, tfile):
+        def stylise(_, t_u8):
+            if args.style_size:
+                t_f32 = wct.resize_u8(t_u8, synthesis_shape(int(t_u8.shape[0]), int(t_u8.shape[1]), args.style_size), to_tensor=True, filter="bicubic")
+            else:
+                t_f32 = wct.to_tensor_u8(t_u8)
+            H, W = synthesis_noise_shape(*size) if size is not None else (int(t_f32.shape[2]), int(t_f32.shape[3]))
+
+            def once(fresh):        # nothing to remake: the recompute reuses the texture tensor
+                res = wct.synthesize(t_f32, H, W, seed=args.seed, stream_id=i, alpha=args.alpha, num_run=args.num_run)
+                return res[:, :, :size[0], :size[1]] if size is not None else res
+            return _recompute_fp32(wct, logprinter, "texture", once)
+
+        return Job(' #%s: Transferring "%s"' % (i, tfile.split(".")[0] + ".jpg"), None,
+                   lambda _: _upload_u8(os.path.join(args.texturePath, tfile)), stylise, synthesis_out_name(args, tfile))
+
+    return _run_jobs(args, wct, logprinter, [job(i, t) for i, t in enumerate(jobs)]), len(jobs)
 
 
 class LogPrinter:     # WCT.py:78-82
@@ -1027,18 +942,90 @@ def _fp32_fallback(wct, args, logprinter, c_f32, style_u8_dev):
     match here; luma is applied by the caller's _finish_u8)."""
     logprinter("WARNING: f16x3 range exceeded for this pair -> recomputing it with exact-fp32 convolutions")
     wct.set_conv_mode("fp32")
-    if getattr(args, "preserve_color", None) == "match":
-        res = wct.stylize_color(c_f32, _to_tensor(wct, style_u8_dev, args.style_size), "match", args.alpha, args.num_run)
-    else:
-        res = wct.stylize(c_f32, _to_tensor(wct, style_u8_dev, args.style_size), args.alpha, args.num_run)
-    wct.sync()
-    wct.set_conv_mode("f16x3")
+    try:
+        if getattr(args, "preserve_color", None) == "match":
+            res = wct.stylize_color(c_f32, _to_tensor(wct, style_u8_dev, args.style_size), "match", args.alpha, args.num_run)
+        else:
+            res = wct.stylize(c_f32, _to_tensor(wct, style_u8_dev, args.style_size), args.alpha, args.num_run)
+        wct.sync()
+    finally:
+        wct.set_conv_mode("f16x3")
     return res
+
+
+def _recompute_fp32(wct, logprinter, noun, once, sync=True):
+    """The result of once(False) -- or, when that pass clamped an activation at the f16x3 range (+-65504), of once(True) under the
+    exact-fp32 convolutions: never a silent deviation from the fp32 reference.  `once(fresh)` stylises one `noun` (pair, content,
+    texture); fresh = make the style tensors anew.  sync: wct.sync() behind the second pass -- it raises OverflowError if that one
+    clamped too.  The engine is back in f16x3 however the recompute ends."""
+    res = once(False)
+    if wct.saturation_count(reset=True):
+        logprinter("WARNING: f16x3 range exceeded for this %s -> recomputing it with exact-fp32 convolutions" % noun)
+        wct.set_conv_mode("fp32")
+        try:
+            res = once(True)
+            if sync:
+                wct.sync()
+        finally:
+            wct.set_conv_mode("f16x3")
+    return res
+
+
+def _on_device(array, pin=False):
+    """A host array on the device; pin = through pinned memory, asynchronously."""
+    import torch
+    t = torch.from_numpy(array)
+    return t.pin_memory().cuda(non_blocking=True) if pin else t.cuda()
+
+
+def _upload_u8(path):
+    """Decode `path` to uint8 HWC and send it off to the device: a decoded frame crosses PCIe as it is (3 B/px, pinned); Resize and
+    ToTensor run on the GPU."""
+    return _on_device(load_rgb_u8(path), pin=True)
+
+
+def _device_images(limit):
+    """fetch(path): _upload_u8(path), keeping the last `limit` images on the device (the oldest is dropped first)."""
+    held = {}
+
+    def fetch(path):
+        u8 = held.get(path)
+        if u8 is None:
+            u8 = held[path] = _upload_u8(path)
+            while len(held) > limit:
+                held.pop(next(iter(held)))
+        return u8
+    return fetch
+
+
+# One job of the serial loop: header = its log line behind the asterisks; content = the content's path (None: there is none);
+# before(c_u8) = an optional step after the upload and outside the timer, whose result goes to stylise (label map, weight maps, the
+# pair's decoded style); stylise(c_f32, that result) = the cascade with its fp32 recompute (_recompute_fp32); out = the file to write.
+Job = collections.namedtuple("Job", "header content before stylise out")
+
+
+def _run_jobs(args, wct, logprinter, jobs) -> float:
+    """The reference's loop (WCT.py:112-131) for every mode that takes one job at a time; its timer covers the conversion of the content,
+    the cascade and the save.  Returns the summed per-job time."""
+    from PIL import Image
+    total = 0.0
+    for job in jobs:
+        logprinter("\n" + "*" * 30 + job.header)
+        c_u8 = _upload_u8(job.content) if job.content else None
+        extra = job.before(c_u8) if job.before else None
+        t0 = time.time()
+        c_f32 = _to_tensor(wct, c_u8, args.content_size) if job.content else None
+        res = job.stylise(c_f32, extra)
+        out = _finish_u8(wct, args, res, c_f32).cpu().numpy()   # .cpu() syncs
+        Image.fromarray(out).save(job.out)
+        dt = time.time() - t0
+        total += dt
+        logprinter("Elapsed time is: %.4f seconds" % dt)
+    return total
 
 
 def run_serial(args, wct, pairs, content_dir, style_dir, logprinter) -> float:
     """The reference's loop (WCT.py:112-131), one pair at a time; returns the summed per-pair time (cascade + save, like its timer)."""
-    import torch
     from PIL import Image
     avg = 0.0
     # style statistics are computed once per style image and reused for every content it is paired with
@@ -1047,20 +1034,17 @@ def run_serial(args, wct, pairs, content_dir, style_dir, logprinter) -> float:
     # --preserve_color match: the matched style depends on the content, so there are no statistics to cache -- every pair matches and
     # prepares its own style (wct_stylize_color); the decoded style stays on the device (uint8, the last few) instead
     match = getattr(args, "preserve_color", None) == "match"
-    style_dev = {}
+    on_device = _device_images(8)
     for i, (cfile, sfile) in enumerate(pairs):
         imname = pair_name(cfile, sfile)
         logprinter("\n" + "*" * 30 + ' #%s: Transferring "%s"' % (i, imname))
-        # decoded uint8 frames cross PCIe as they are (3 B/px, pinned); Resize and ToTensor run on the GPU
-        c_u8 = torch.from_numpy(load_rgb_u8(os.path.join(content_dir, cfile))).pin_memory().cuda(non_blocking=True)
-        s_u8 = style_dev.get(sfile) if match else None
-        if s_u8 is None and (match or sfile not in style_cache):
-            s_u8 = torch.from_numpy(load_rgb_u8(os.path.join(style_dir, sfile))).pin_memory().cuda(non_blocking=True)
+        c_u8 = _upload_u8(os.path.join(content_dir, cfile))
+        if match:
+            s_u8 = on_device(os.path.join(style_dir, sfile))
+        else:
+            s_u8 = _upload_u8(os.path.join(style_dir, sfile)) if sfile not in style_cache else None
         t0 = time.time()
         if match:
-            style_dev[sfile] = s_u8
-            while len(style_dev) > 8:
-                style_dev.pop(next(iter(style_dev)))
             c_f32 = _to_tensor(wct, c_u8, args.content_size)
             res = wct.stylize_color(c_f32, _to_tensor(wct, s_u8, args.style_size), "match", args.alpha, args.num_run)
         elif s_u8 is not None:
@@ -1074,7 +1058,7 @@ def run_serial(args, wct, pairs, content_dir, style_dir, logprinter) -> float:
             res = wct.stylize_prepared(c_f32, args.alpha, args.num_run)
         if wct.saturation_count(reset=True):
             if s_u8 is None:
-                s_u8 = torch.from_numpy(load_rgb_u8(os.path.join(style_dir, sfile))).cuda()
+                s_u8 = _upload_u8(os.path.join(style_dir, sfile))
             res = _fp32_fallback(wct, args, logprinter, c_f32, s_u8)
             style_cache.pop(sfile, None)          # its cached statistics may carry the clamp too
         out = _finish_u8(wct, args, res, c_f32).cpu().numpy()   # .cpu() syncs
@@ -1094,7 +1078,6 @@ def run_pipelined(args, wct, pairs, content_dir, style_dir, logprinter) -> float
     (counter in stream order, copied with the image) when the pair leaves that window; a clamped pair is recomputed in exact fp32
     and everything enqueued after it is discarded and redone (its style statistics may carry the clamp) -- the serial loop's
     results.  Returns the wall time of the whole run."""
-    import collections
     import concurrent.futures as cf
     import torch
     from PIL import Image
@@ -1151,7 +1134,7 @@ def run_pipelined(args, wct, pairs, content_dir, style_dir, logprinter) -> float
             sfile = rec["sfile"]
             s_u8 = style_dev.get(sfile)
             if s_u8 is None:
-                s_u8 = torch.from_numpy(load_rgb_u8(os.path.join(style_dir, sfile))).cuda()
+                s_u8 = _upload_u8(os.path.join(style_dir, sfile))
             res = _fp32_fallback(wct, args, logprinter, rec["c_f32"], s_u8)
             rec["host"].copy_(_finish_u8(wct, args, res, rec["c_f32"]))
             rec["ev"] = torch.cuda.Event()
@@ -1236,6 +1219,42 @@ def run_pipelined(args, wct, pairs, content_dir, style_dir, logprinter) -> float
     return time.time() - t_start
 
 
+def pair_jobs(args, content_dir, style_dir) -> List[Tuple[str, str]]:
+    return list_pairs(content_dir, style_dir, args.picked_content_mark, args.picked_style_mark)
+
+
+def _number_of(what):
+    return lambda jobs: "Number of %s: %s" % (what, len(jobs))
+
+
+# The modes that take one job at a time, in their order of precedence; whatever none of them takes is a plain run (run_pipelined or
+# run_serial).  chosen(args): this mode runs; reason: the rest of its "--pipeline is ignored with" line; jobs(args, content_dir,
+# style_dir) and early: its job list and when main() makes it; number(jobs): its "Number of" line; noun: what the closing average is
+# per; run(args, wct, jobs, content_dir, style_dir, logprinter) -> (total seconds, images written).
+Mode = collections.namedtuple("Mode", "name chosen reason jobs early number noun run")
+MODES = (
+    Mode("synthesis", lambda a: a.synthesis, "--synthesis: texture synthesis uses the serial loop",
+         lambda a, c, s: texture_jobs(a.texturePath), False, _number_of("content-style pairs"), "pair", run_synthesis),
+    Mode("regions", lambda a: a.maskPath is not None, "--maskPath: region runs use the serial loop",
+         lambda a, c, s: region_jobs(c, a.maskPath, a.picked_content_mark), True, _number_of("contents with label maps"), "image", run_regions),
+    Mode("interp", lambda a: a.interp_styles is not None, "--interp_styles: interpolation and weight-map runs use the serial loop",
+         interp_jobs, False, _number_of("contents"), "image", run_interp),
+    Mode("video", lambda a: a.video, "--video: a sequence is stylised frame by frame, each against the one before",
+         video_jobs, False, lambda jobs: "Number of frames: %s, styles: %s" % (len(jobs[0]), len(jobs[1])), "frame", run_video),
+    Mode("swap", lambda a: a.swap_level, "--swap_level: patch-swap runs use the serial loop",
+         pair_jobs, True, _number_of("content-style pairs"), "pair", run_swap),
+    Mode("scale", lambda a: a.level_scale, "--level_scale: scale-controlled runs use the serial loop",
+         pair_jobs, True, _number_of("content-style pairs"), "pair", run_scale),
+    Mode("auto", lambda a: a.auto_regions, "--auto_regions: feature-region runs use the serial loop",
+         pair_jobs, True, _number_of("content-style pairs"), "pair", run_auto),
+)
+
+
+def select_mode(args) -> Optional[Mode]:
+    """The first mode of MODES that `args` choose; None for a plain content x style run."""
+    return next((m for m in MODES if m.chosen(args)), None)
+
+
 def main(argv: Optional[List[str]] = None) -> int:
     args = build_parser().parse_args(argv)
     checkpoint_args(args)
@@ -1255,70 +1274,29 @@ def main(argv: Optional[List[str]] = None) -> int:
     logprinter(sorted(vars(args).items()))
     content_dir = args.UHD_contentPath if args.UHD else args.contentPath
     style_dir = args.UHD_stylePath if args.UHD else args.stylePath
-    if args.synthesis:
+    mode = select_mode(args)
+    if mode is not None:
+        # early: the jobs are listed before the engine exists (a missing label map refuses the run there) and counted in the log ahead
+        # of the --pipeline note; the other modes list and count theirs behind it
+        jobs = mode.jobs(args, content_dir, style_dir) if mode.early else None
         from .wct import WCT
         wct = WCT(args)
+        if mode.early:
+            logprinter(mode.number(jobs))
         if args.pipeline > 0:
-            logprinter("--pipeline is ignored with --synthesis: texture synthesis uses the serial loop")
-        avg, n = run_synthesis(args, wct, logprinter)
+            logprinter("--pipeline is ignored with " + mode.reason)
+        if not mode.early:
+            jobs = mode.jobs(args, content_dir, style_dir)
+            logprinter(mode.number(jobs))
+        total, n = mode.run(args, wct, jobs, content_dir, style_dir, logprinter)
         if n:
-            logprinter("Processed %d images. Average processing time per pair is: %.4f seconds" % (n, avg / n))
+            logprinter("Processed %d images. Average processing time per %s is: %.4f seconds" % (n, mode.noun, total / n))
         return 0
-    if args.maskPath is not None:
-        jobs = region_jobs(content_dir, args.maskPath, args.picked_content_mark)
-        from .wct import WCT
-        wct = WCT(args)
-        logprinter("Number of contents with label maps: %s" % len(jobs))
-        if args.pipeline > 0:
-            logprinter("--pipeline is ignored with --maskPath: region runs use the serial loop")
-        avg = run_regions(args, wct, content_dir, logprinter)
-        if jobs:
-            logprinter("Processed %d images. Average processing time per image is: %.4f seconds" % (len(jobs), avg / len(jobs)))
-        return 0
-    if args.interp_styles is not None:
-        from .wct import WCT
-        wct = WCT(args)
-        if args.pipeline > 0:
-            logprinter("--pipeline is ignored with --interp_styles: interpolation and weight-map runs use the serial loop")
-        avg, n = run_interp(args, wct, content_dir, logprinter)
-        if n:
-            logprinter("Processed %d images. Average processing time per image is: %.4f seconds" % (n, avg / n))
-        return 0
-    if args.video:
-        from .wct import WCT
-        wct = WCT(args)
-        if args.pipeline > 0:
-            logprinter("--pipeline is ignored with --video: a sequence is stylised frame by frame, each against the one before")
-        avg, n = run_video(args, wct, content_dir, style_dir, logprinter)
-        if n:
-            logprinter("Processed %d images. Average processing time per frame is: %.4f seconds" % (n, avg / n))
-        return 0
-    pairs = list_pairs(content_dir, style_dir, args.picked_content_mark, args.picked_style_mark)
+    pairs = pair_jobs(args, content_dir, style_dir)
 
     from .wct import WCT      # raises ImportError if libwct_hip.so is missing: no CPU fallback
     wct = WCT(args)
     logprinter("Number of content-style pairs: %s" % len(pairs))
-    if args.swap_level:
-        if args.pipeline > 0:
-            logprinter("--pipeline is ignored with --swap_level: patch-swap runs use the serial loop")
-        avg = run_swap(args, wct, pairs, content_dir, style_dir, logprinter)
-        if pairs:
-            logprinter("Processed %d images. Average processing time per pair is: %.4f seconds" % (len(pairs), avg / len(pairs)))
-        return 0
-    if args.level_scale:
-        if args.pipeline > 0:
-            logprinter("--pipeline is ignored with --level_scale: scale-controlled runs use the serial loop")
-        avg = run_scale(args, wct, pairs, content_dir, style_dir, logprinter)
-        if pairs:
-            logprinter("Processed %d images. Average processing time per pair is: %.4f seconds" % (len(pairs), avg / len(pairs)))
-        return 0
-    if args.auto_regions:
-        if args.pipeline > 0:
-            logprinter("--pipeline is ignored with --auto_regions: feature-region runs use the serial loop")
-        avg = run_auto(args, wct, pairs, content_dir, style_dir, logprinter)
-        if pairs:
-            logprinter("Processed %d images. Average processing time per pair is: %.4f seconds" % (len(pairs), avg / len(pairs)))
-        return 0
     if args.pipeline > 0:
         wall = run_pipelined(args, wct, pairs, content_dir, style_dir, logprinter)
         if pairs:
