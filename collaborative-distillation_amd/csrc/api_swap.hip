@@ -124,17 +124,26 @@ int swap_bufs(wct_ctx* ctx, int C, int h, int w, int hs, int ws, bool whitened) 
   return WCT_OK;
 }
 
-// dst = W (feat - mu), W = cov^(-1/2) of the map itself: wct_moments + wct_transform_solve(WCT_TRANSFORM_WCT, [I, 0], alpha = 1) + wct_apply_labeled
-int swap_whiten(wct_ctx* ctx, const float* feat, int C, int h, int w, float* dst) {
+}  // namespace
+
+// (W, -W mu) of a map, W = cov^(-1/2) of the map itself, into the context's (M, b), and its raw moments into the main lane's sums:
+// wct_moments + wct_transform_solve(WCT_TRANSFORM_WCT, [I, 0], alpha = 1).  Shared with the attention statistics' whitened domain (api_attn.hip).
+int wct_host::whiten_solve(wct_ctx* ctx, const float* feat, int C, int h, int w, SumsView& sv, double** M, double** b) {
   Lane& ln = ctx->main;
-  SumsView sv;
   if (int rc = sums_view(ctx, ln, sv)) return rc;
-  double *M, *b;
-  if (int rc = mb_view(ctx, &M, &b)) return rc;
+  if (int rc = mb_view(ctx, M, b)) return rc;
   if (int rc = moments_impl(ctx, ln, feat, C, h, w, 0, w, sv.sum, sv.sumsq)) return rc;
-  if (int rc = solve_against_slot(ctx, WCT_TRANSFORM_WCT, C, (double)h * w, sv.sum, sv.sumsq, nullptr, 1.0, M, b, sv.info)) return rc;
+  return solve_against_slot(ctx, WCT_TRANSFORM_WCT, C, (double)h * w, sv.sum, sv.sumsq, nullptr, 1.0, *M, *b, sv.info);
+}
+
+namespace {
+// dst = W (feat - mu): whiten_solve + wct_apply_labeled with one label
+int swap_whiten(wct_ctx* ctx, const float* feat, int C, int h, int w, float* dst) {
+  SumsView sv;
+  double *M, *b;
+  if (int rc = whiten_solve(ctx, feat, C, h, w, sv, &M, &b)) return rc;
   const long npix = (long)h * w;
-  HIPCHK(ctx, hipMemsetAsync(ctx->swLab.p, 0, (size_t)npix, ln.stream));
+  HIPCHK(ctx, hipMemsetAsync(ctx->swLab.p, 0, (size_t)npix, ctx->main.stream));
   return apply_labeled_impl(ctx, feat, C, npix, reinterpret_cast<const uint8_t*>(ctx->swLab.p), 1, M, b, dst);
 }
 

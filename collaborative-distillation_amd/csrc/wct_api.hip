@@ -818,6 +818,13 @@ int wct_debug_set(wct_ctx* ctx, const char* key, double value) {
     ctx->swap_key_chunk = (int)value;
     return WCT_OK;
   }
+  else if (!strcmp(key, "attn_query_chunk")) {
+    // queries per launch of wct_attn_stats (0: the default WCT_ATTN_QUERY_CHUNK).  Results do not depend on it: a test / measurement key
+    if (!getenv("WCT_DEBUG")) return fail(ctx, WCT_ERR_INVALID, "debug_set: 'attn_query_chunk' is a test / measurement key; set WCT_DEBUG to allow it");
+    if (value < 0 || value > 2147483647.0 || value != (double)(long)value) return fail(ctx, WCT_ERR_INVALID, "debug_set: 'attn_query_chunk' takes a query count >= 1, or 0 for the default");
+    ctx->attn_query_chunk = (int)value;
+    return WCT_OK;
+  }
   else if (!strcmp(key, "clip_channels")) {
     // TEST KEY (include/wct_hip_video.h): clips created from now on hold `value` channels at every level instead of the loaded encoders'
     // (0: off) -- the tracking step on its own at widths no loadable encoder has; wct_stylize_clip refuses such a clip
@@ -849,7 +856,7 @@ int wct_debug_set(wct_ctx* ctx, const char* key, double value) {
     ctx->side.stream = ns;
     return WCT_OK;
   }
-  else return fail(ctx, WCT_ERR_INVALID, "debug_set: unknown key '%s' (fuse, sp, l1fuse, u8fuse, upconv, fastfold, interleave, foldgemm, nscoop, in3wide, mom32, eig_skip, side_priority, poison, prof_forms, swap_key_chunk, clip_channels)", key);
+  else return fail(ctx, WCT_ERR_INVALID, "debug_set: unknown key '%s' (fuse, sp, l1fuse, u8fuse, upconv, fastfold, interleave, foldgemm, nscoop, in3wide, mom32, eig_skip, side_priority, poison, prof_forms, swap_key_chunk, attn_query_chunk, clip_channels)", key);
   HIPCHK(ctx, hipStreamSynchronize(ctx->side.stream));
   return WCT_OK;
 }

@@ -173,6 +173,20 @@ hipError_t launch_patch_match(const float* q, int h, int w, const float* k, int 
                               void* run, size_t run_bytes, float* rnorm, size_t norm_bytes, unsigned* sat, hipStream_t s);
 hipError_t launch_patch_assemble(const int32_t* idx, int h, int w, const float* v, int hs, int ws, int C, const float* base, float alpha, float* out,
                                  hipStream_t s);
+// ---- attention-weighted style statistics (attn.hip; include/wct_hip_attn.h).  launch_attn_diag: (M, b) of the standardised map -- M diagonal,
+// C x C -- and (mu, sigma) (may be null) from raw moments; launch_attn_unit: unit rows; launch_attn_stats: the maximum of |v| and the scale of
+// v^2 into `scratch` (the float part of attn_stat_bytes), then one launch per `query_chunk` queries; launch_attn_apply: the elementwise result.
+__attribute__((visibility("hidden"))) size_t attn_stat_bytes(int C);   // mu [C] | sigma [C] doubles, then 1024 partial maxima | scale | 1 / scale
+__attribute__((visibility("hidden"))) hipError_t launch_attn_diag(int C, double n, double eps, const double* sum, const double* sumsq, double* M, double* b,
+                                                                  double* mu_out, double* sigma_out, hipStream_t s);
+// out = fp32(W (x - sum / npix)), fp64 throughout; Mt [C * C] receives the transpose of M = W
+__attribute__((visibility("hidden"))) hipError_t launch_attn_whiten(const float* x, long npix, int C, const double* sum, const double* M, double* Mt,
+                                                                    float* out, hipStream_t s);
+__attribute__((visibility("hidden"))) hipError_t launch_attn_unit(const float* in, long n, int C, float* out, hipStream_t s);
+__attribute__((visibility("hidden"))) hipError_t launch_attn_stats(const float* qhat, int Nq, const float* khat, const float* v, int Nk, int C, float tau,
+                                                                   int query_chunk, float* mean, float* var, float* scratch, hipStream_t s);
+__attribute__((visibility("hidden"))) hipError_t launch_attn_apply(const float* mean, const float* var, const float* c_std, const float* cF, long n, int C,
+                                                                   const double* mu_s, const double* sigma_s, float alpha, float* out, hipStream_t s);
 // *dst = (double)*counter on the stream (wct_range_flag_f64: the saturation counter as a value a sharded run can all-reduce)
 hipError_t launch_counter_to_f64(const unsigned* counter, double* dst, hipStream_t s);
 // ---- image edge: transforms.Resize = Pillow's bilinear resampler, bit-exact (resize.hip)

@@ -120,6 +120,11 @@ struct wct_ctx {
   // (score, index) of every query between the key chunks' launches, the key norms, and the all-zero label map of the one-label affine apply
   DevBuf swFc, swFs, swQ, swK, swOut, swIdx, swRun, swNorm, swLab;
   int swap_key_chunk = 0;   // debug key "swap_key_chunk": keys per launch of the match; 0 = WCT_SWAP_KEY_CHUNK
+  // attention statistics (include/wct_hip_attn.h): the two encoded features, the standardised maps and the unit rows of both sides, the
+  // whitened map in front of its unit rows, (mean, var), the blended feature, and [mu_s | sigma_s | partial maxima of |V| | scale of V^2]
+  // ... and the transposed whitening matrix of the whitened domain [C * C doubles]
+  DevBuf atFc, atFs, atCs, atSs, atQ, atK, atProj, atMean, atVar, atOut, atStat, atMt;
+  int attn_query_chunk = 0;   // debug key "attn_query_chunk": queries per launch of the statistics; 0 = WCT_ATTN_QUERY_CHUNK
   // scale control (include/wct_hip_scale.h): the content at the working size of every distinct divisor of wct_stylize_scaled, and the
   // image its merges and levels ping-pong through with the caller's `out`
   DevBuf scF[5], scStage, scTab;   // scTab: the weight tables of one resampler / merge launch (scale.hip)
@@ -207,6 +212,7 @@ struct wct_ctx {
     for (Lane* ln : {&main, &side})
       for (DevBuf* b : {&ln->actA, &ln->actB, &ln->wsMom, &ln->wsEig, &ln->sums}) f(*b, ln, true);
     for (DevBuf* b : {&featS, &tmpT, &wsAsm, &trBuf, &small, &foldW, &foldW16, &eigC, &u8c, &u8s, &u8o, &rsz_tmp, &noise, &colStyle, &colOut, &colWs, &smSums, &smAB, &swFc, &swFs, &swQ, &swK, &swOut, &swIdx, &swRun, &swNorm, &swLab, &packed,
+                      &atFc, &atFs, &atCs, &atSs, &atQ, &atK, &atProj, &atMean, &atVar, &atOut, &atStat, &atMt,
                       &shIn, &shOut, &shNext, &shEdge, &shStyle, &shStats, &shMb,
                       &regLab, &regHist, &regSums, &regMb, &regFeat, &wsRegMom, &wsRegApply,
                       &blendW, &blendStat, &wsBlendPool, &wsBlendApply, &gdLab, &gdHist, &kmFeatC, &kmFeatS, &kmWs, &kmStat, &motionWs})
@@ -323,6 +329,8 @@ void free_module(Module& m);
 void release_comm(wct_ctx* ctx);   // wct_destroy: destroys a communicator the context owns
 // api_video.hip
 __attribute__((visibility("hidden"))) int clip_track_level(wct_ctx* ctx, wct_clip* clip, int level, int C, double* sum, double* sumsq);   // the tracking step of wct_stylize_clip's frame: nothing committed
+// api_swap.hip
+__attribute__((visibility("hidden"))) int whiten_solve(wct_ctx* ctx, const float* feat, int C, int h, int w, SumsView& sv, double** M, double** b);   // needs eigS[0] sized by the caller
 // api_multi.hip
 int apply_labeled_impl(wct_ctx* ctx, const float* feat, int C, long npix, const uint8_t* lab, int K, const double* M, const double* b, float* out);
 

@@ -36,7 +36,10 @@ with the uint8 conversion fused into whichever kernel comes last.  The files car
 every 3x3 patch of the content feature is replaced by its best-matching style feature patch, matched in the whitened domains of both
 features (--swap_match whitened, the default) or on the features themselves (raw); the other levels keep --transform.  One pair at a time
 (wct_stylize_swap, the serial loop: the swapped level needs the style's feature map, not its statistics); --preserve_color luma and
---smooth_radius follow as usual.  The files carry _swap=<L> in their names, after the transform mark.
+--smooth_radius follow as usual.  The files carry _swap=<L> in their names, after the transform mark.  --swap_match attention |
+attention_whitened replaces the hard match by attention-weighted style statistics (include/wct_hip_attn.h: every content position takes
+the style mean and deviation under a softmax of feature similarity, temperature --swap_temp T in 0..32, default 8; wct_stylize_attn, the
+same loop); those files carry _swap=<L>_<match>=<T>.
 --level_scale d5,d4,d3,d2,d1 (not in the reference; Gatys et al. 2017, section 6: scale control) runs level L on the content reduced by the
 divisor dL and, where the working size grows, brings the running image up and puts the content's fine detail back (--scale_detail, a look);
 --coarse_style gives the reduced levels a style of their own (scale mixing).  One pair at a time (wct_stylize_scaled, the serial loop);
@@ -139,9 +142,14 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--swap_level", type=int, default=None, choices=[2, 3, 4, 5],
                    help="run this level of the cascade as a patch swap (style decorator): every 3x3 content feature patch is replaced by "
                         "its best-matching style patch; the other levels keep --transform (default: off)")
-    p.add_argument("--swap_match", type=str, default=None, choices=["whitened", "raw"],
+    p.add_argument("--swap_match", type=str, default=None, choices=["whitened", "raw", "attention", "attention_whitened"],
                    help="where --swap_level matches patches: whitened = in the whitened domains of both features (Avatar-Net's style "
-                        "decorator, the default), raw = on the features themselves (Chen & Schmidt)")
+                        "decorator, the default), raw = on the features themselves (Chen & Schmidt); attention / attention_whitened = no "
+                        "hard match at all: every content position takes the style mean and deviation weighted by a softmax of feature "
+                        "similarity (on the standardised / the whitened features; include/wct_hip_attn.h)")
+    p.add_argument("--swap_temp", type=float, default=None,
+                   help="with --swap_match attention | attention_whitened: the softmax temperature, 0 .. 32 (0 = AdaIN with the population "
+                        "variance, large = a 1x1 nearest-feature swap; default 8)")
     # not in the reference: scale control, a coarse-to-fine cascade on a device image pyramid (include/wct_hip_scale.h)
     p.add_argument("--level_scale", type=str, default=None,
                    help="d5,d4,d3,d2,d1: run level L of the cascade on the content reduced by the integer divisor dL (1 .. 16, not "
@@ -222,6 +230,8 @@ def out_name(args, imname: str) -> str:
     swap = getattr(args, "swap_level", None)
     if swap:
         tmark += "_swap=%d" % swap                                                              # after the transform mark
+        if getattr(args, "swap_match", None) in ATTN_MATCH_NAMES:                               # the patch swap's names are unchanged
+            tmark += "_%s=%g" % (args.swap_match, getattr(args, "swap_temp", None) or 0.0)
     scale = getattr(args, "level_scale", None)
     if scale:
         tmark += "_scale=%s" % "-".join(t.strip() for t in scale.split(","))                    # in the same place (the two do not mix)
@@ -442,11 +452,17 @@ def check_transform_args(args) -> None:
             raise ValueError("--transform %s does not mix with %s (defined for the wct transform only)" % (transform, name))
 
 
+ATTN_MATCH_NAMES = ("attention", "attention_whitened")       # lib.ATTN_MATCHES: the --swap_match values that route to wct_stylize_attn
+
+
 def check_swap_args(args) -> None:
     """--swap_level L / --swap_match: one style per content, a content to take patches for, and the plain cascade around the swapped
     level; --preserve_color luma and --smooth_radius are post-steps and go with it.  Fills in the default match."""
-    from .lib import SWAP_LEVELS, SWAP_MATCHES
+    from .lib import ATTN_MAX_TEMP, ATTN_TEMP, SWAP_LEVELS, SWAP_MATCHES
     level, match = getattr(args, "swap_level", None), getattr(args, "swap_match", None)
+    temp = getattr(args, "swap_temp", None)
+    if temp is not None and match not in ATTN_MATCH_NAMES:
+        raise ValueError("--swap_temp needs --swap_level with --swap_match attention or attention_whitened")
     if not level:
         if match is not None:
             raise ValueError("--swap_match does nothing without --swap_level")
@@ -455,6 +471,11 @@ def check_swap_args(args) -> None:
         raise ValueError("--swap_level: one of %s expected, got %r" % (", ".join(str(v) for v in SWAP_LEVELS), level))
     if match is None:
         args.swap_match = "whitened"
+    elif match in ATTN_MATCH_NAMES:
+        if temp is None:
+            args.swap_temp = ATTN_TEMP
+        elif not 0.0 <= temp <= ATTN_MAX_TEMP:           # a NaN fails both comparisons
+            raise ValueError("--swap_temp: a temperature in 0 .. %d expected, got %r" % (ATTN_MAX_TEMP, temp))
     elif match not in SWAP_MATCHES:
         raise ValueError("--swap_match: whitened or raw expected, got %r" % (match,))
     clash = [name for flag, name in ((args.synthesis, "--synthesis"), (args.maskPath is not None, "--maskPath"),
@@ -472,6 +493,8 @@ def _swap_pair(wct, args, logprinter, c_f32, style_f32):
 
     def once(fresh):
         passes.append(fresh)
+        if args.swap_match in ATTN_MATCH_NAMES:
+            return wct.stylize_attn(c_f32, style_f32(), args.swap_level, args.swap_match, args.swap_temp, args.alpha, args.num_run)
         return wct.stylize_swap(c_f32, style_f32(), args.swap_level, args.swap_match, args.alpha, args.num_run)
 
     # no wct.sync() in the recompute: it raises on a clamp; saturation_count synchronises, counts and acknowledges it instead
@@ -492,7 +515,9 @@ def run_swap(args, wct, pairs, content_dir, style_dir, logprinter) -> Tuple[floa
 
     def job(i, cfile, sfile):
         imname = pair_name(cfile, sfile)
-        return Job(' #%s: Transferring "%s" (patch swap at level %d, %s)' % (i, imname, args.swap_level, args.swap_match),
+        what = "attention statistics at level %d, %s, temperature %g" % (args.swap_level, args.swap_match, args.swap_temp) \
+            if args.swap_match in ATTN_MATCH_NAMES else "patch swap at level %d, %s" % (args.swap_level, args.swap_match)
+        return Job(' #%s: Transferring "%s" (%s)' % (i, imname, what),
                    os.path.join(content_dir, cfile), lambda c_u8: on_device(os.path.join(style_dir, sfile)), stylise, out_name(args, imname))
 
     return _run_jobs(args, wct, logprinter, [job(i, c, s) for i, (c, s) in enumerate(pairs)]), len(pairs)

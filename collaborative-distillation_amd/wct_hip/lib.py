@@ -57,6 +57,15 @@ SWAP_EPS = 1e-12                                                    # WCT_SWAP_E
 SWAP_KEY_CHUNK = 8192                                               # WCT_SWAP_KEY_CHUNK
 SWAP_LEVELS = (2, 3, 4, 5)
 
+# every symbol include/wct_hip_attn.h declares (attention-weighted style statistics at one cascade level); bound from the same libwct_hip.so
+SYMBOLS_ATTN = ["wct_attn_project", "wct_attn_stats", "wct_attn_apply", "wct_attn_level", "wct_stylize_attn"]
+ATTN_STANDARD, ATTN_WHITENED = 0, 1                                 # WCT_ATTN_*: the match domain
+ATTN_MATCHES = {"attention": ATTN_STANDARD, "attention_whitened": ATTN_WHITENED}   # --swap_match names -> domain
+ATTN_EPS = 1e-12                                                    # WCT_ATTN_EPS
+ATTN_MAX_TEMP = 32                                                  # WCT_ATTN_MAX_TEMP
+ATTN_QUERY_TILE, ATTN_KEY_TILE, ATTN_QUERY_CHUNK = 64, 32, 32768    # WCT_ATTN_QUERY_TILE, WCT_ATTN_KEY_TILE, WCT_ATTN_QUERY_CHUNK
+ATTN_TEMP = 8.0                                                     # the command line's default --swap_temp
+
 # every symbol include/wct_hip_scale.h declares (scale control: the coarse-to-fine cascade on a device image pyramid); bound from the same libwct_hip.so
 SYMBOLS_SCALE = ["wct_scale_shape", "wct_resample_planar", "wct_pyramid_merge", "wct_stylize_scaled"]
 SCALE_MAX_DIVISOR = 16                                              # WCT_SCALE_MAX_DIVISOR
@@ -224,6 +233,11 @@ def load() -> ctypes.CDLL:
     lib.wct_patch_assemble.argtypes = [c_void_p, vp, c_int, c_int, vp, c_int, c_int, c_int, vp, c_float, vp]
     lib.wct_swap_level.argtypes = [c_void_p, c_int, vp, c_int, c_int, vp, c_int, c_int, c_int, c_float, vp, ip, ip]
     lib.wct_stylize_swap.argtypes = [c_void_p, vp, c_int, c_int, vp, c_int, c_int, c_int, c_int, c_float, c_int, vp, ip, ip]
+    lib.wct_attn_project.argtypes = [c_void_p, vp, c_int, c_int, c_int, c_int, vp, vp]
+    lib.wct_attn_stats.argtypes = [c_void_p, vp, c_int, vp, vp, c_int, c_int, c_float, vp, vp]
+    lib.wct_attn_apply.argtypes = [c_void_p, vp, vp, vp, vp, c_int, c_int, vp, vp, c_float, vp]
+    lib.wct_attn_level.argtypes = [c_void_p, c_int, vp, c_int, c_int, vp, c_int, c_int, c_int, c_float, c_float, vp, ip, ip]
+    lib.wct_stylize_attn.argtypes = [c_void_p, vp, c_int, c_int, vp, c_int, c_int, c_int, c_int, c_float, c_float, c_int, vp, ip, ip]
     lib.wct_scale_shape.argtypes = [c_int, c_int, c_int, ip, ip]
     lib.wct_resample_planar.argtypes = [c_void_p, vp, c_int, c_int, vp, c_int, c_int, c_int]
     lib.wct_pyramid_merge.argtypes = [c_void_p, vp, vp, c_int, c_int, vp, c_int, c_int, c_float, vp]

@@ -997,6 +997,98 @@ class WCT:
         self._style_keep = s      # the side stream reads it asynchronously
         return out.view(-1)[: 3 * ho.value * wo.value].view(1, 3, ho.value, wo.value)
 
+    # ------------------------------------------------------------------ attention statistics (include/wct_hip_attn.h)
+    @staticmethod
+    def _attn_domain(what: str, match: str) -> int:
+        if match not in _lib.ATTN_MATCHES:
+            raise ValueError("%s: match must be one of %s, got %r" % (what, ", ".join(repr(m) for m in _lib.ATTN_MATCHES), match))
+        return _lib.ATTN_MATCHES[match]
+
+    @torch.no_grad()
+    def attn_project(self, feat: torch.Tensor, match: str = "attention", want_std: bool = True):
+        """The unit rows of the NHWC map `feat` [1,h,w,C] projected into the match domain ("attention": the standardised map,
+        "attention_whitened": the whitened map of the patch swap), and with want_std the standardised map (wct_attn_project):
+        (unit, std) or unit, each [1,h,w,C] fp32."""
+        domain = self._attn_domain("attn_project", match)
+        f = self._nhwc(feat)
+        h, w, C = (int(v) for v in f.shape)
+        unit = torch.empty((1, h, w, C), device=f.device, dtype=torch.float32)
+        std = torch.empty((1, h, w, C), device=f.device, dtype=torch.float32) if want_std else None
+        self._stream()
+        self._chk(self._lib.wct_attn_project(self._ctx, f.data_ptr(), h, w, C, domain, unit.data_ptr(), std.data_ptr() if want_std else None))
+        return (unit, std) if want_std else unit
+
+    @torch.no_grad()
+    def attn_stats(self, qhat: torch.Tensor, khat: torch.Tensor, v: torch.Tensor, tau: float):
+        """Per query row of `qhat` [Nq,C] the softmax(tau <q^, k^>)-weighted mean and variance of the value rows `v` [Nk,C] over the
+        key rows `khat` [Nk,C] (wct_attn_stats): (mean, var), each [Nq,C] fp32.  No Nq x Nk matrix exists anywhere."""
+        q, k, vv = (self._dev_f32(t.reshape(-1, t.shape[-1])) for t in (qhat, khat, v))
+        Nq, C = (int(t) for t in q.shape)
+        Nk = int(k.shape[0])
+        if tuple(k.shape) != (Nk, C) or tuple(vv.shape) != (Nk, C):
+            raise ValueError("attn_stats: qhat %s, khat %s and v %s do not agree" % (tuple(q.shape), tuple(k.shape), tuple(vv.shape)))
+        mean = torch.empty((Nq, C), device=q.device, dtype=torch.float32)
+        var = torch.empty((Nq, C), device=q.device, dtype=torch.float32)
+        self._stream()
+        self._chk(self._lib.wct_attn_stats(self._ctx, q.data_ptr(), Nq, k.data_ptr(), vv.data_ptr(), Nk, C, float(tau), mean.data_ptr(), var.data_ptr()))
+        return mean, var
+
+    @torch.no_grad()
+    def attn_apply(self, mean: torch.Tensor, var: torch.Tensor, c_std: torch.Tensor, cF: torch.Tensor, mu_s: torch.Tensor,
+                   sigma_s: torch.Tensor, alpha: Optional[float] = None) -> torch.Tensor:
+        """alpha (sigma_s (sqrt(var) c_std + mean) + mu_s) + (1 - alpha) cF per position (wct_attn_apply); the four maps [n,C] (or
+        NHWC) fp32, mu_s and sigma_s [C] fp64.  Returns a tensor shaped like cF."""
+        alpha = self.alpha if alpha is None else float(alpha)
+        C = int(cF.shape[-1])
+        m, vr, z, x = (self._dev_f32(t.reshape(-1, C)) for t in (mean, var, c_std, cF))
+        n = int(x.shape[0])
+        if not all(tuple(t.shape) == (n, C) for t in (m, vr, z)):
+            raise ValueError("attn_apply: the four maps must have one shape")
+        mu = self._dev_f64(mu_s, C, "attn_apply: mu_s")
+        sg = self._dev_f64(sigma_s, C, "attn_apply: sigma_s")
+        out = torch.empty((n, C), device=x.device, dtype=torch.float32)
+        self._stream()
+        self._chk(self._lib.wct_attn_apply(self._ctx, m.data_ptr(), vr.data_ptr(), z.data_ptr(), x.data_ptr(), n, C, mu.data_ptr(), sg.data_ptr(),
+                                           alpha, out.data_ptr()))
+        return out.view(cF.shape)
+
+    @torch.no_grad()
+    def attn_level(self, level: int, contentImg: torch.Tensor, styleImg: torch.Tensor, match: str = "attention", tau: float = _lib.ATTN_TEMP,
+                   alpha: Optional[float] = None) -> torch.Tensor:
+        """One level with attention-weighted style statistics instead of one affine transform (wct_attn_level): encode both images,
+        give every content position the softmax-weighted style mean and deviation, blend with the content feature by alpha, decode."""
+        domain = self._attn_domain("attn_level", match)
+        alpha = self.alpha if alpha is None else float(alpha)
+        c, s = self._img(contentImg), self._img(styleImg)
+        H, W, Hs, Ws = int(c.shape[1]), int(c.shape[2]), int(s.shape[1]), int(s.shape[2])
+        lv = int(level) if int(level) in (1, 2, 3, 4, 5) else 1
+        out = torch.empty((1, 3, (H >> (lv - 1)) << (lv - 1), (W >> (lv - 1)) << (lv - 1)), device=c.device, dtype=torch.float32)
+        ho, wo = c_int(), c_int()
+        self._stream()
+        self._chk(self._lib.wct_attn_level(self._ctx, int(level), c.data_ptr(), H, W, s.data_ptr(), Hs, Ws, domain, float(tau), alpha,
+                                           out.data_ptr(), byref(ho), byref(wo)))
+        assert (ho.value, wo.value) == tuple(out.shape[2:])
+        return out
+
+    @torch.no_grad()
+    def stylize_attn(self, contentImg: torch.Tensor, styleImg: torch.Tensor, attn_level: int, match: str = "attention",
+                     tau: float = _lib.ATTN_TEMP, alpha: Optional[float] = None, num_run: int = 1,
+                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The 5 -> 1 cascade with level `attn_level` (2..5) run through attn_level() and every other level through
+        style_transfer_level() under the context's transform, one library call (wct_stylize_attn); bit-identical to that
+        composition."""
+        domain = self._attn_domain("stylize_attn", match)
+        alpha = self.alpha if alpha is None else float(alpha)
+        c, s = self._img(contentImg), self._img(styleImg)
+        H, W, Hs, Ws = int(c.shape[1]), int(c.shape[2]), int(s.shape[1]), int(s.shape[2])
+        out = self._out_image(out, H, W)
+        ho, wo = c_int(), c_int()
+        self._stream()
+        self._chk(self._lib.wct_stylize_attn(self._ctx, c.data_ptr(), H, W, s.data_ptr(), Hs, Ws, int(attn_level), domain, float(tau), alpha,
+                                             int(num_run), out.data_ptr(), byref(ho), byref(wo)))
+        self._style_keep = s      # the side stream reads it asynchronously
+        return out.view(-1)[: 3 * ho.value * wo.value].view(1, 3, ho.value, wo.value)
+
     # ------------------------------------------------------------------ scale control (include/wct_hip_scale.h)
     @staticmethod
     def scale_shape(H: int, W: int, divisor: int):
