@@ -37,6 +37,11 @@ int wct_set_transform(wct_ctx* ctx, int mode) {
   WCT_GUARD(ctx);
   if (mode != WCT_TRANSFORM_WCT && mode != WCT_TRANSFORM_OT && mode != WCT_TRANSFORM_ADAIN) return fail(ctx, WCT_ERR_INVALID, "set_transform: mode %d outside 0..2", mode);
   if (mode != WCT_TRANSFORM_WCT && ctx->numpy_variant) return fail(ctx, WCT_ERR_INVALID, "set_transform: the numpy variant (+ I on cov_c) is defined for the wct transform only");
+  if (mode != WCT_TRANSFORM_WCT)
+    for (int level = 1; level <= 5; ++level)
+      if (ctx->rotated[level])
+        return fail(ctx, WCT_ERR_STATE, "set_transform: the style slot of level %d is rotated (wct_style_diversify), which the wct transform alone reads as it is meant; "
+                    "prepare or import the style again first", level);
   ctx->transform = mode;
   return WCT_OK;
 }

@@ -11,25 +11,10 @@
 // into a larger buffer need not be), four 4-byte stores otherwise; the last block of an image whose 3 H W is not a multiple of 4 is
 // partial.  20 32 x 32 -> 64-bit multiplies per 16 bytes stored: the arithmetic hides behind the stores (see launch_noise_uniform).
 #include "wct_common.h"
+#include "philox_dev.h"
 #include <algorithm>
 
 namespace {
-
-constexpr unsigned PHILOX_M0 = 0xD2511F53u, PHILOX_M1 = 0xCD9E8D57u;   // multipliers
-constexpr unsigned PHILOX_W0 = 0x9E3779B9u, PHILOX_W1 = 0xBB67AE85u;   // Weyl increments of the key
-
-struct Philox4 { unsigned v[4]; };
-
-__host__ __device__ inline Philox4 philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const unsigned long long p0 = (unsigned long long)PHILOX_M0 * c0, p1 = (unsigned long long)PHILOX_M1 * c2;
-    const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1;
-    c0 = n0; c1 = (unsigned)p1; c2 = n2; c3 = (unsigned)p0;
-    k0 += PHILOX_W0; k1 += PHILOX_W1;
-  }
-  return Philox4{{c0, c1, c2, c3}};
-}
 
 // grid-stride over the blocks of four elements; `total` = 3 H W
 __global__ __launch_bounds__(256) void noise_uniform_kernel(unsigned k0, unsigned k1, unsigned stream_id, unsigned long long total, float* out) {

@@ -11,10 +11,11 @@
 //            launch_ot_assemble   Q = Z S, then T = S Q, M and b by one workgroup per 16 rows
 //   adain  T = diag(sqrt((cov_s_ii + eps) / (cov_c_ii + eps))),  cov_s_ii = SUM_k S_ik^2:  one launch, no matrix function.
 //
-// GEMM tiles: one wave per 16 x 16 output tile, operands straight from global memory (C <= 512: every matrix is L2 resident), any
-// even C -- rows, columns and k past C read as zero and are not written.  Every sum has a fixed order: results are functions of the
-// inputs alone.
+// GEMM tiles (mm_f64_dev.h): one wave per 16 x 16 output tile, operands straight from global memory (C <= 512: every matrix is L2
+// resident), any even C -- rows, columns and k past C read as zero and are not written.  Every sum has a fixed order: results are
+// functions of the inputs alone.
 #include "wct_common.h"
+#include "mm_f64_dev.h"
 
 namespace {
 
@@ -23,30 +24,6 @@ __device__ __forceinline__ double cov_entry(int r, int c, int C, double n, const
   const double mr = sum[r] / n, mc = sum[c] / n;
   const int lo = r < c ? r : c, hi = r < c ? c : r;
   return (sumsq[(size_t)lo * C + hi] - n * mr * mc) / (n - 1.0);
-}
-
-// acc += A[i0 .. i0+15][0 .. C) B[0 .. C)[j0 .. j0+15]; A(r, k) and B(k, c) are called inside the matrix only.
-// Result layout (as solve.hip tile_gemm): acc[reg] is row i0 + (lane >> 4) + 4 reg, column j0 + (lane & 15).
-template <class FA, class FB>
-__device__ __forceinline__ f64x4 tile_mm(FA A, FB B, int C, int i0, int j0, int lane, f64x4 acc) {
-  const int li = lane & 15, kk = lane >> 4;
-  const int ra = i0 + li, cb = j0 + li;
-  for (int k0 = 0; k0 < C; k0 += 4) {
-    const int k = k0 + kk;
-    const double a = (ra < C && k < C) ? A(ra, k) : 0.0;
-    const double b = (cb < C && k < C) ? B(k, cb) : 0.0;
-    acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc, 0, 0, 0);
-  }
-  return acc;
-}
-
-// this wave's tile of a grid of 4-wave workgroups over nt x nt tiles; false: no tile
-__device__ __forceinline__ bool wave_tile(int C, int& i0, int& j0) {
-  const int nt = (C + 15) >> 4;
-  const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (t >= nt * nt) return false;
-  i0 = (t / nt) * 16; j0 = (t % nt) * 16;
-  return true;
 }
 
 // D = L R  (COV: L = cov_c from the raw moments (n, sum, sumsq); otherwise L is a C x C matrix)
@@ -137,8 +114,6 @@ __global__ __launch_bounds__(256) void adain_assemble_kernel(int C, double alpha
     if (a == 0 && info) *info = 0;     // no matrix function on the content side
   }
 }
-
-inline unsigned tile_blocks(int C) { const unsigned nt = (unsigned)((C + 15) / 16); return (nt * nt + 3) / 4; }
 
 }  // namespace
 

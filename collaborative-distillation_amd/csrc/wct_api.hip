@@ -461,8 +461,11 @@ bool fast_fold_level(const wct_ctx* ctx, int level) {
 }
 
 // the style-side part of the fast fold for `level`, on `st`, from the style EigResult in ctx->eigS[level] (F = cov_s^(1/2), mu_s)
+// Everything that rewrites a slot ends here, so this is also where the slot stops counting as rotated (wct_style_diversify sets the mark
+// again behind its own call).
 int style_fold(wct_ctx* ctx, int level, hipStream_t st) {
   ctx->fold_ready[level] = false;
+  ctx->rotated[level] = false;
   if (!fast_fold_level(ctx, level)) return WCT_OK;
   const LayerDev& l = ctx->mod[WCT_KIND_DEC][level].layers[0];
   const size_t C = l.d.cin, cc = C * C;

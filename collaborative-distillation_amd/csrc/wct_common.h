@@ -290,6 +290,15 @@ hipError_t launch_ot_assemble(int C, double alpha, const double* S, const double
 hipError_t launch_adain_assemble(int C, double alpha, double eps, const double* S, const double* mu_s, double n, const double* sum_c, const double* sumsq_c,
                                  double* M, double* b, int* info_dev, hipStream_t s);
 
+// ---- the seeded rotation of style diversification (rotate.hip; include/wct_hip_diverse.h), fp64, C even, 2..512
+//   launch_rotation_make   Z [C*C] = the Cayley transform of the seeded skew matrix A (skew [C*C], may be null, receives A); strength 0 writes
+//                          I and needs no workspace; C > 128 synchronises the stream inside launch_eig (the outcome of the deflated iteration)
+//   launch_rotation_apply  out = F Z (out overlaps neither)
+__attribute__((visibility("hidden"))) size_t rotation_workspace_bytes(int C);   // A | B | U | zeros | EigResult | launch_eig's workspace | info
+__attribute__((visibility("hidden"))) hipError_t launch_rotation_make(int C, unsigned long long seed, unsigned stream_id, unsigned tag, double strength, double* Z,
+                                                                      double* skew, void* workspace, size_t workspace_bytes, hipStream_t s);
+__attribute__((visibility("hidden"))) hipError_t launch_rotation_apply(int C, const double* F, const double* Z, double* out, hipStream_t s);
+
 // ---- fold csF = M x + b into a decoder's first conv:  W' = W o M, b' = bias + W o b
 //      w_oihw: device [cout][cin][3][3] fp32 (original weights), out: packed weights + bias for ConvDesc
 //      maxbits_dev (optional): receives max |W'| as float bits for launch_split_pack(..., have_max = true)

@@ -202,6 +202,11 @@ struct wct_ctx {
   // motion compensation (include/wct_hip_motion.h), the standalone entries: [pyramid of cur | pyramid of prev | the coarser levels' fields]
   DevBuf motionWs;
   int clip_channels = 0;               // debug key "clip_channels": the channel count of every level of clips created from now on; 0: the loaded encoders'
+  // style diversification (include/wct_hip_diverse.h): the rotation's workspace (rotate.hip rotation_workspace_bytes) and [Z C*C | the slot's F
+  // before the product C*C]; neither is part of wct_reserve / wct_workspace_bytes.  rotated[level]: the slot holds F Z, no longer the symmetric
+  // cov_s^(1/2) -- set by wct_style_diversify, cleared by style_fold, which everything that rewrites a slot ends with
+  DevBuf dvWs, dvZ;
+  bool rotated[6] = {false, false, false, false, false, false};
 
   // EVERY DevBuf of the context, once, with its class: f(buf, owning lane, scratch).  Scratch = no later call is documented to read
   // what an earlier call left there, so the "poison" hook may overwrite it between calls; state must survive (style slots, the
@@ -215,7 +220,7 @@ struct wct_ctx {
                       &atFc, &atFs, &atCs, &atSs, &atQ, &atK, &atProj, &atMean, &atVar, &atOut, &atStat, &atMt,
                       &shIn, &shOut, &shNext, &shEdge, &shStyle, &shStats, &shMb,
                       &regLab, &regHist, &regSums, &regMb, &regFeat, &wsRegMom, &wsRegApply,
-                      &blendW, &blendStat, &wsBlendPool, &wsBlendApply, &gdLab, &gdHist, &kmFeatC, &kmFeatS, &kmWs, &kmStat, &motionWs})
+                      &blendW, &blendStat, &wsBlendPool, &wsBlendApply, &gdLab, &gdHist, &kmFeatC, &kmFeatS, &kmWs, &kmStat, &motionWs, &dvWs, &dvZ})
       f(*b, &main, true);
     for (DevBuf* b : {&gdSums, &wsGdMom}) f(*b, &side, true);   // the guided call's style side
     for (DevBuf& b : scF) f(b, &main, true);

@@ -54,6 +54,12 @@ looks, not measurements.  The style is prepared once, the frames run one at a ti
 and --mode original do not.  One image per frame under the usual name.  --motion (with --video) estimates a block-matched motion field
 between consecutive frames (--motion_levels, --motion_range, --motion_penalty) and blends against the previous frame displaced by it
 (wct_motion_attach): panning and moving regions keep their strokes as the still ones do.
+--diversity D (not in the reference; Wang et al., "Diversified Arbitrary Style Transfer via Deep Feature Perturbation", CVPR 2020) gives
+several takes on one pair: the style's square-root covariance of --diversity_levels (default 5) is post-multiplied by a seeded rotation of
+strength D in (0, 8] before the colouring step (wct_style_diversify: the same target statistics through a different map); --variations N
+writes N images per pair, variation k from stream id k of --seed.  The style is prepared once per pair, one image at a time (the serial
+loop); --alpha, --num_run, --preserve_color luma, --smooth_radius and --video (one rotation for the whole clip) go with it, --transform
+ot | adain and the other modes do not.  The files carry _div=<D> after the transform mark and, with N > 1, _v<k> before the pair name.
 Decoding/encoding files needs Pillow on the host (the reference's own dependency); the GPU library is mandatory: there
 is no CPU fallback.
 """
@@ -187,6 +193,16 @@ def build_parser() -> argparse.ArgumentParser:
                    help="with --motion: search range at the coarsest level in its pixels, 0 .. 7 (default 4)")
     p.add_argument("--motion_penalty", type=int, default=None,
                    help="with --motion: cost per pixel of vector length, in grey levels, 0 .. 255 (default 4)")
+    # not in the reference: seeded style variations, a rotation inside the colouring step (include/wct_hip_diverse.h)
+    p.add_argument("--diversity", type=float, default=None,
+                   help="D in (0, 8]: post-multiply the style's square-root covariance by a seeded rotation of this strength before the "
+                        "colouring step (Wang et al., CVPR 2020): same feature statistics, a different stylisation per --seed and variation "
+                        "(default: off)")
+    p.add_argument("--variations", type=int, default=None,
+                   help="with --diversity: images per pair, 1 .. 64 (default 1); variation k uses stream id k of --seed and is saved as _v<k>")
+    p.add_argument("--diversity_levels", type=str, default=None,
+                   help="with --diversity: comma-separated cascade levels whose style is rotated (default 5, the paper's choice; a look, "
+                        "not a measurement)")
     return p
 
 
@@ -221,12 +237,14 @@ def pair_name(content_file: str, style_file: str) -> str:
     return content_file.split(".")[0] + "+" + style_file.split(".")[0] + ".jpg"
 
 
-def out_name(args, imname: str) -> str:
-    """WCT.py:127 (str(1) for the integer default of --alpha, like '%s' % args.alpha there)."""
+def out_name(args, imname: str, variation: Optional[int] = None) -> str:
+    """WCT.py:127 (str(1) for the integer default of --alpha, like '%s' % args.alpha there).  variation: the k of --variations N > 1."""
     color = getattr(args, "preserve_color", None)
     radius = getattr(args, "smooth_radius", 0)
     transform = getattr(args, "transform", None) or "wct"
     tmark = "_transform=%s" % transform if transform != "wct" else ""                          # directly after alpha; wct names are unchanged
+    if getattr(args, "diversity", None):
+        tmark += "_div=%g" % args.diversity                                                     # after the transform mark (wct only, so: in its place)
     swap = getattr(args, "swap_level", None)
     if swap:
         tmark += "_swap=%d" % swap                                                              # after the transform mark
@@ -239,6 +257,8 @@ def out_name(args, imname: str) -> str:
     if auto:
         tmark += "_auto=%d" % auto                                                              # in the same place (mixes with neither)
     marks = ("_color=%s" % color if color else "") + ("_smooth=%d" % radius if radius else "")   # runs with and without the flags never collide
+    if variation is not None:
+        marks += "_v%d" % variation                                                              # directly before the pair name
     return os.path.join(args.outf, "%s_mode=%s_alpha=%s%s%s_%s" % (args.log_mark, args.mode, args.alpha, tmark, marks, imname))
 
 
@@ -608,6 +628,83 @@ def run_scale(args, wct, pairs, content_dir, style_dir, logprinter) -> Tuple[flo
     return _run_jobs(args, wct, logprinter, [job(i, c, s) for i, (c, s) in enumerate(pairs)]), len(pairs)
 
 
+def diversity_level_list(text: str) -> Tuple[int, ...]:
+    """'5,4' -> (5, 4): the levels of --diversity_levels."""
+    try:
+        levels = tuple(int(t) for t in text.split(","))
+    except ValueError:
+        raise ValueError("--diversity_levels: comma-separated levels among 1..5 expected, got %r" % (text,)) from None
+    if not levels or any(not 1 <= L <= 5 for L in levels) or len(set(levels)) != len(levels):
+        raise ValueError("--diversity_levels: distinct levels among 1..5 expected, got %r" % (text,))
+    return levels
+
+
+def check_diverse_args(args) -> None:
+    """--diversity D / --variations N / --diversity_levels: ordinary content x style pairs (or the frames of --video, one variation)
+    through the wct cascade against prepared statistics; --alpha, --num_run, --preserve_color luma and --smooth_radius go with it.
+    Fills in the defaults; --diversity_levels becomes a tuple of levels."""
+    from .lib import DIVERSE_LEVELS, DIVERSE_MAX_STRENGTH
+    D, N, levels = getattr(args, "diversity", None), getattr(args, "variations", None), getattr(args, "diversity_levels", None)
+    if D is None:
+        for v, name in ((N, "--variations"), (levels, "--diversity_levels")):
+            if v is not None:
+                raise ValueError("%s does nothing without --diversity" % name)
+        return
+    if not 0.0 < D <= DIVERSE_MAX_STRENGTH:              # a NaN fails both comparisons
+        raise ValueError("--diversity: a strength in (0, %d] expected, got %r" % (DIVERSE_MAX_STRENGTH, D))
+    if N is not None and not 1 <= N <= 64:
+        raise ValueError("--variations: 1 .. 64 expected, got %r" % (N,))
+    parsed = DIVERSE_LEVELS if levels is None else levels if isinstance(levels, tuple) else diversity_level_list(levels)
+    if not 0 <= args.seed < 1 << 64:
+        raise ValueError("--seed: 0 .. 2^64 - 1 expected, got %d" % args.seed)
+    transform = getattr(args, "transform", None) or "wct"
+    clash = [name for flag, name in ((transform != "wct", "--transform %s" % transform), (args.numpy, "--numpy"), (args.synthesis, "--synthesis"),
+                                     (args.maskPath is not None, "--maskPath"), (args.interp_styles is not None, "--interp_styles"),
+                                     (args.weightPath is not None, "--weightPath"), (getattr(args, "swap_level", None), "--swap_level"),
+                                     (getattr(args, "level_scale", None), "--level_scale"), (getattr(args, "auto_regions", None), "--auto_regions"),
+                                     (getattr(args, "preserve_color", None) == "match", "--preserve_color match")) if flag]
+    if clash:
+        raise ValueError("--diversity does not mix with %s" % ", ".join(clash))
+    if getattr(args, "video", False) and N not in (None, 1):
+        raise ValueError("--video takes one variation of --diversity (the same rotation for every frame), got --variations %d" % N)
+    args.variations = 1 if N is None else N
+    args.diversity_levels = parsed
+
+
+def run_diverse(args, wct, pairs, content_dir, style_dir, logprinter) -> Tuple[float, int]:
+    """--diversity: per pair the style is prepared once and the slots of --diversity_levels exported; every variation v imports them
+    again, rotates them (wct_style_diversify: --seed, stream id v) and runs the cascade against the prepared statistics.  One job of
+    the serial loop per image.  Returns (total seconds, images)."""
+    on_device = _device_images(8)
+    levels, N = args.diversity_levels, args.variations
+    held = {}                   # the pair whose style the engine holds: {"pair": i, "slots": {level: its statistics before any rotation}}
+
+    def job(i, cfile, sfile, v):
+        imname = pair_name(cfile, sfile)
+
+        def stylise(c_f32, s_u8):
+            def once(fresh):        # the recompute prepares the style again, and what it prepared is not kept for the next variation
+                if fresh or held.get("pair") != i:
+                    held.clear()
+                    wct.style_prepare(_to_tensor(wct, s_u8, args.style_size))
+                    if not fresh:
+                        held.update(pair=i, slots={L: wct.style_export(L) for L in levels})
+                else:
+                    for L, stats in held["slots"].items():
+                        wct.style_import(L, stats)
+                wct.style_diversify(args.diversity, args.seed, v, levels)
+                return wct.stylize_prepared(c_f32, args.alpha, args.num_run)
+            return _recompute_fp32(wct, logprinter, "pair", once)
+
+        return Job(' #%s: Transferring "%s" (diversity %g at level%s %s, variation %d of %d)' % (
+                       i * N + v, imname, args.diversity, "s" if len(levels) > 1 else "", ",".join(str(L) for L in levels), v, N),
+                   os.path.join(content_dir, cfile), lambda c_u8: on_device(os.path.join(style_dir, sfile)), stylise,
+                   out_name(args, imname, v if N > 1 else None))
+
+    jobs = [job(i, c, s, v) for i, (c, s) in enumerate(pairs) for v in range(N)]
+    return _run_jobs(args, wct, logprinter, jobs), len(jobs)
+
+
 VIDEO_FLAGS = (("temporal_rate", "--temporal_rate"), ("scene_cut", "--scene_cut"), ("temporal_blend", "--temporal_blend"),
                ("temporal_sigma", "--temporal_sigma"), ("temporal_radius", "--temporal_radius"))
 
@@ -714,6 +811,8 @@ def run_video(args, wct, jobs, content_dir, style_dir, logprinter) -> Tuple[floa
     avg, n = 0.0, 0
     for sfile in styles:
         wct.style_prepare(_to_tensor(wct, _upload_u8(os.path.join(style_dir, sfile)), args.style_size))
+        if getattr(args, "diversity", None):          # once per clip: every frame is coloured through the same rotation
+            wct.style_diversify(args.diversity, args.seed, 0, args.diversity_levels)
         clip =wct.clip(H, W, args.temporal_rate, args.scene_cut, args.temporal_blend, args.temporal_sigma, args.temporal_radius, motion=motion)
         try:
             for i, cfile in enumerate(frames):
@@ -909,8 +1008,8 @@ def synthesis_noise_shape(H: int, W: int) -> Tuple[int, int]:
 
 def check_synthesis_args(args) -> None:
     if not args.synthesis:
-        if args.seed != 0:
-            raise ValueError("--seed needs --synthesis")
+        if args.seed != 0 and getattr(args, "diversity", None) is None:
+            raise ValueError("--seed needs --synthesis or --diversity")
         if args.synthesis_size is not None:
             raise ValueError("--synthesis_size needs --synthesis")
         return
@@ -1275,9 +1374,15 @@ MODES = (
 )
 
 
+# --diversity is a variation of the plain run, not of any mode above (of those only --video goes with it, and keeps its own loop): it is
+# looked at last, behind the table
+DIVERSE_MODE = Mode("diverse", lambda a: getattr(a, "diversity", None), "--diversity: variations of a pair use the serial loop",
+                    pair_jobs, True, _number_of("content-style pairs"), "image", run_diverse)
+
+
 def select_mode(args) -> Optional[Mode]:
-    """The first mode of MODES that `args` choose; None for a plain content x style run."""
-    return next((m for m in MODES if m.chosen(args)), None)
+    """The first mode of MODES that `args` choose, then --diversity; None for a plain content x style run."""
+    return next((m for m in MODES + (DIVERSE_MODE,) if m.chosen(args)), None)
 
 
 def main(argv: Optional[List[str]] = None) -> int:
@@ -1294,6 +1399,7 @@ def main(argv: Optional[List[str]] = None) -> int:
     check_auto_args(args)
     check_video_args(args)
     check_motion_args(args)
+    check_diverse_args(args)
     os.makedirs(args.outf, exist_ok=True)
     logprinter = LogPrinter(args.debug, os.path.join(args.outf, "log_%s_%s.txt" % (args.log_mark, args.mode)))
     logprinter(sorted(vars(args).items()))

@@ -91,6 +91,11 @@ SYMBOLS_MOTION = ["wct_motion_shape", "wct_motion_luma", "wct_motion_estimate", 
 MOTION_BLOCK, MOTION_MAX_LEVELS, MOTION_MAX_RANGE = 8, 4, 7         # WCT_MOTION_BLOCK, WCT_MOTION_MAX_LEVELS, WCT_MOTION_MAX_RANGE
 MOTION_LEVELS, MOTION_RANGE, MOTION_PENALTY = 4, 4, 4               # WCT_MOTION_*: the command line's defaults
 
+# every symbol include/wct_hip_diverse.h declares (seeded style variations: a rotation inside the colouring step); bound from the same libwct_hip.so
+SYMBOLS_DIVERSE = ["wct_rotation_make", "wct_style_diversify", "wct_stylize_diverse"]
+DIVERSE_MAX_STRENGTH = 8                                            # WCT_DIVERSE_MAX_STRENGTH
+DIVERSE_LEVELS = (5,)                                               # the command line's default --diversity_levels
+
 
 class WctLayer(ctypes.Structure):
     _fields_ = [("cin", c_int), ("cout", c_int), ("pool_after", c_int), ("up_after", c_int),
@@ -261,6 +266,10 @@ def load() -> ctypes.CDLL:
     lib.wct_motion_blend.argtypes = [c_void_p, vp, c_int, c_int, vp, vp, vp, c_int, c_int, c_float, c_float, c_int, vp, vp, vp, c_int, vp]
     lib.wct_motion_attach.argtypes = [c_void_p, c_void_p, POINTER(WctMotionParams)]
     lib.wct_motion_export.argtypes = [c_void_p, c_void_p, vp]
+    lib.wct_rotation_make.argtypes = [c_void_p, c_int, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint, c_double, vp, vp]
+    lib.wct_style_diversify.argtypes = [c_void_p, ctypes.c_uint, c_double, ctypes.c_uint64, ctypes.c_uint32]
+    lib.wct_stylize_diverse.argtypes = [c_void_p, vp, c_int, c_int, vp, c_int, c_int, ctypes.c_uint, c_double, ctypes.c_uint64, ctypes.c_uint32, c_float, c_int,
+                                        vp, ip, ip]
     lib.wct_set_transform.argtypes = [c_void_p, c_int]
     lib.wct_get_transform.argtypes = [c_void_p, ip]
     lib.wct_transform_solve.argtypes = [c_void_p, c_int, c_int, c_double, vp, vp, vp, c_double, vp, vp, ip]

@@ -440,6 +440,62 @@ class WCT:
         self._chk(self._lib.wct_stylize_prepared(self._ctx, c.data_ptr(), H, W, alpha, int(num_run), out.data_ptr(), byref(ho), byref(wo)))
         return out.view(-1)[: 3 * ho.value * wo.value].view(1, 3, ho.value, wo.value)
 
+    # ------------------------------------------------------------------ seeded style variations (include/wct_hip_diverse.h)
+    @staticmethod
+    def _diverse_args(what: str, strength, seed, stream_id, levels=None):
+        strength, seed, stream_id = float(strength), int(seed), int(stream_id)
+        if not (0.0 <= strength <= _lib.DIVERSE_MAX_STRENGTH):
+            raise ValueError("%s: strength must lie in [0, %d], got %r" % (what, _lib.DIVERSE_MAX_STRENGTH, strength))
+        if not (0 <= seed < 1 << 64) or not (0 <= stream_id < 1 << 32):
+            raise ValueError("%s: seed must fit 64 bits and stream_id 32 bits (unsigned), got %d, %d" % (what, seed, stream_id))
+        mask = 0
+        for L in () if levels is None else levels:
+            if int(L) not in (1, 2, 3, 4, 5):
+                raise ValueError("%s: levels must be among 1..5, got %r" % (what, tuple(levels)))
+            mask |= 1 << int(L)
+        if levels is not None and not mask:
+            raise ValueError("%s: no level given" % what)
+        return strength, seed, stream_id, mask
+
+    @torch.no_grad()
+    def rotation(self, C: int, strength: float, seed: int = 0, stream_id: int = 0, tag: int = 0, want_skew: bool = False):
+        """The orthogonal Z(C, seed, stream_id, tag, strength) [C, C] fp64 of include/wct_hip_diverse.h (the Cayley transform of a seeded
+        skew-symmetric A; the identity at strength 0), a function of its arguments alone, bit for bit.  want_skew: -> (Z, A)."""
+        strength, seed, stream_id, _ = self._diverse_args("rotation", strength, seed, stream_id)
+        C, tag = int(C), int(tag)
+        if C < 2 or C % 2 or C > 512 or not (0 <= tag <= 255):
+            raise ValueError("rotation: C even in 2..512 and tag in 0..255 expected, got C=%d, tag=%d" % (C, tag))
+        Z = torch.empty(C, C, device=self.stats_device, dtype=torch.float64)
+        A = torch.empty(C, C, device=self.stats_device, dtype=torch.float64) if want_skew else None
+        self._stream()
+        self._chk(self._lib.wct_rotation_make(self._ctx, C, seed, stream_id, tag, strength, Z.data_ptr(), A.data_ptr() if want_skew else None))
+        return (Z, A) if want_skew else Z
+
+    def style_diversify(self, strength: float, seed: int = 0, stream_id: int = 0, levels=(5,)):
+        """Post-multiply the prepared style slots of `levels` by the seeded rotation (tag = level), in place: the same target covariance
+        through a different colouring map, so everything that reads prepared statistics afterwards (stylize_prepared, clips, style_export,
+        ...) gives a variation.  wct transform only; two calls compose; whatever rewrites a slot (style_prepare, style_import, ...) resets it;
+        strength 0 changes nothing."""
+        strength, seed, stream_id, mask = self._diverse_args("style_diversify", strength, seed, stream_id, levels)
+        self._stream()
+        self._chk(self._lib.wct_style_diversify(self._ctx, mask, strength, seed, stream_id))
+
+    @torch.no_grad()
+    def stylize_diverse(self, contentImg: torch.Tensor, styleImg: torch.Tensor, strength: float, seed: int = 0, stream_id: int = 0, levels=(5,),
+                        alpha: Optional[float] = None, num_run: int = 1, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """style_prepare + style_diversify + stylize_prepared in one library call (wct_stylize_diverse), bit-identical to the three."""
+        alpha = self.alpha if alpha is None else float(alpha)
+        strength, seed, stream_id, mask = self._diverse_args("stylize_diverse", strength, seed, stream_id, levels)
+        c, s = self._img(contentImg), self._img(styleImg)
+        self._style_keep = s      # the side stream reads it asynchronously
+        H, W, Hs, Ws = int(c.shape[1]), int(c.shape[2]), int(s.shape[1]), int(s.shape[2])
+        out = self._out_image(out, H, W)
+        ho, wo = c_int(), c_int()
+        self._stream()
+        self._chk(self._lib.wct_stylize_diverse(self._ctx, c.data_ptr(), H, W, s.data_ptr(), Hs, Ws, mask, strength, seed, stream_id, alpha, int(num_run),
+                                                out.data_ptr(), byref(ho), byref(wo)))
+        return out.view(-1)[: 3 * ho.value * wo.value].view(1, 3, ho.value, wo.value)
+
     # ------------------------------------------------------------------ image edge (ToTensor / save_image on the device)
     def _u8(self, img: torch.Tensor) -> torch.Tensor:
         if img.dtype != torch.uint8 or img.dim() != 3 or img.shape[2] != 3:

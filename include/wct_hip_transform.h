@@ -61,7 +61,8 @@ extern "C" {
 #define WCT_ADAIN_EPS 1e-5           /* model_cd.py:22 */
 
 /* The context's transform (default WCT_TRANSFORM_WCT).  A mode outside 0..2 is WCT_ERR_INVALID; so is a non-wct mode while the numpy
- * variant is on.  Prepared style slots stay valid across a change of mode. */
+ * variant is on.  Prepared style slots stay valid across a change of mode -- except slots rotated by wct_style_diversify
+ * (wct_hip_diverse.h), which only the wct transform reads as they are meant: a non-wct mode is WCT_ERR_STATE while one is rotated. */
 int wct_set_transform(wct_ctx* ctx, int mode);
 int wct_get_transform(const wct_ctx* ctx, int* mode);
 
