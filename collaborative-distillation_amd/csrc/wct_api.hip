@@ -797,6 +797,7 @@ int wct_debug_set(wct_ctx* ctx, const char* key, double value) {
   else if (!strcmp(key, "interleave")) ctx->interleave = v;
   else if (!strcmp(key, "foldgemm")) ctx->foldgemm = v;
   else if (!strcmp(key, "prof_forms")) ctx->prof_forms = v;
+  else if (!strcmp(key, "bgrid_lds")) ctx->bgrid_lds = v;       // 0: wct_bgrid_slice reads the grid from global memory in every tile (same bits)
   else if (!strcmp(key, "nscoop")) ctx->nscoop = (int)value;      // 0: multi-launch, 1: single launch, 2: single launch with an injected placement fault
   else if (!strcmp(key, "mom32")) ctx->mom32 = (int)value;       // 0 / 1 / 2, see wct_ctx
   else if (!strcmp(key, "in3wide")) ctx->in3wide = (int)value;   // 2 / 1 / 0, see wct_ctx
@@ -859,7 +860,7 @@ int wct_debug_set(wct_ctx* ctx, const char* key, double value) {
     ctx->side.stream = ns;
     return WCT_OK;
   }
-  else return fail(ctx, WCT_ERR_INVALID, "debug_set: unknown key '%s' (fuse, sp, l1fuse, u8fuse, upconv, fastfold, interleave, foldgemm, nscoop, in3wide, mom32, eig_skip, side_priority, poison, prof_forms, swap_key_chunk, attn_query_chunk, clip_channels)", key);
+  else return fail(ctx, WCT_ERR_INVALID, "debug_set: unknown key '%s' (fuse, sp, l1fuse, u8fuse, upconv, fastfold, interleave, foldgemm, nscoop, in3wide, mom32, eig_skip, side_priority, poison, prof_forms, swap_key_chunk, attn_query_chunk, clip_channels, bgrid_lds)", key);
   HIPCHK(ctx, hipStreamSynchronize(ctx->side.stream));
   return WCT_OK;
 }

@@ -164,6 +164,15 @@ size_t smooth_sums_bytes(long npix);
 size_t smooth_ab_bytes(long npix);
 hipError_t launch_guided_filter(const float* src, int Ho, int Wo, const float* guide, int Hg, int Wg, int r, double eps, float* out_planar,
                                 uint8_t* out_hwc, int round_mode, double* sums, size_t sums_bytes, float* ab, size_t ab_bytes, hipStream_t s);
+// ---- proxy mode's bilateral grid (bgrid.hip; include/wct_hip_bgrid.h).  launch_bgrid_fit: 5 + 3 smooth launches (one more when a support is taller
+// than one row chunk: bgrid_fit_chunks) on `s`; `ws` (bgrid_fit_workspace_bytes) is the caller's scratch.  launch_bgrid_slice: one launch;
+// use_lds false reads every tile's vertices from global memory (debug key "bgrid_lds": same bits).
+__attribute__((visibility("hidden"))) int bgrid_fit_chunks(int h, int gh);
+__attribute__((visibility("hidden"))) size_t bgrid_fit_workspace_bytes(int h, int gz, int gh, int gw);
+__attribute__((visibility("hidden"))) hipError_t launch_bgrid_fit(const float* cl, const float* sl, int h, int w, int gz, int gh, int gw, double eps,
+                                                                  int smooth, float* grid, double* ws, size_t ws_bytes, hipStream_t s);
+__attribute__((visibility("hidden"))) hipError_t launch_bgrid_slice(const float* grid, int gz, int gh, int gw, const float* content, int H, int W,
+                                                                    float* out_planar, uint8_t* out_hwc, int round_mode, bool use_lds, hipStream_t s);
 // ---- patch swap (swap.hip; include/wct_hip_swap.h).  launch_patch_match: the key norms, then one launch per chunk of `key_chunk` keys, then the
 // read-out; `run` (swap_run_bytes(Nq): the running (score, index) of every query) and `rnorm` (swap_norm_bytes(Nk)) are the caller's scratch; `sat`:
 // the context's saturation counter.  The number of launches is a function of (hs, ws, key_chunk) alone.

@@ -116,6 +116,10 @@ struct wct_ctx {
   // guided-filter smoothing (include/wct_hip_smooth.h): the window sums between the two directions of a box (21 fp64 planes) and the
   // coefficients a, b between the two stages (12 fp32 planes); wct_stylize_smooth keeps its un-filtered result in colOut
   DevBuf smSums, smAB;
+  // proxy mode (include/wct_hip_bgrid.h): the fit's sums and partial sums, and for wct_stylize_proxy the reduced content, its
+  // stylisation and the grid
+  DevBuf bgWs, bgGrid, pxCl, pxSl;
+  int bgrid_lds = 1;   // debug key "bgrid_lds": 0 = the slice reads every tile's vertices from global memory (same bits)
   // patch swap (include/wct_hip_swap.h): the two encoded features, the two projected maps, the blended feature, the indices, the running
   // (score, index) of every query between the key chunks' launches, the key norms, and the all-zero label map of the one-label affine apply
   DevBuf swFc, swFs, swQ, swK, swOut, swIdx, swRun, swNorm, swLab;
@@ -220,7 +224,8 @@ struct wct_ctx {
                       &atFc, &atFs, &atCs, &atSs, &atQ, &atK, &atProj, &atMean, &atVar, &atOut, &atStat, &atMt,
                       &shIn, &shOut, &shNext, &shEdge, &shStyle, &shStats, &shMb,
                       &regLab, &regHist, &regSums, &regMb, &regFeat, &wsRegMom, &wsRegApply,
-                      &blendW, &blendStat, &wsBlendPool, &wsBlendApply, &gdLab, &gdHist, &kmFeatC, &kmFeatS, &kmWs, &kmStat, &motionWs, &dvWs, &dvZ})
+                      &blendW, &blendStat, &wsBlendPool, &wsBlendApply, &gdLab, &gdHist, &kmFeatC, &kmFeatS, &kmWs, &kmStat, &motionWs, &dvWs, &dvZ,
+                      &bgWs, &bgGrid, &pxCl, &pxSl})
       f(*b, &main, true);
     for (DevBuf* b : {&gdSums, &wsGdMom}) f(*b, &side, true);   // the guided call's style side
     for (DevBuf& b : scF) f(b, &main, true);

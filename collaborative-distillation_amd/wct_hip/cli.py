@@ -60,6 +60,13 @@ strength D in (0, 8] before the colouring step (wct_style_diversify: the same ta
 writes N images per pair, variation k from stream id k of --seed.  The style is prepared once per pair, one image at a time (the serial
 loop); --alpha, --num_run, --preserve_color luma, --smooth_radius and --video (one rotation for the whole clip) go with it, --transform
 ot | adain and the other modes do not.  The files carry _div=<D> after the transform mark and, with N > 1, _v<k> before the pair name.
+--proxy_scale D (not in the reference; Chen et al., "Bilateral Guided Upsampling", SIGGRAPH Asia 2016) stylises the content reduced by the
+divisor D in 1..16 and applies the result at full size: from the reduced pair a bilateral grid of local affine colour maps is fitted (one
+vertex per --proxy_cell reduced pixels, --proxy_bins luminance vertices, regulariser --proxy_eps, --proxy_smooth blur passes; the defaults
+are looks) and sliced by the full content (wct_stylize_proxy; include/wct_hip_bgrid.h).  The saved image has the content's exact size and
+its edges; colour and tone are transferred, strokes are not.  One pair at a time (the serial loop); --alpha, --num_run, --transform,
+--content_size, --style_size and --round go with it, the other modes, --diversity, --preserve_color and --smooth_radius do not.  The files
+carry _proxy=<D> after the transform mark.
 Decoding/encoding files needs Pillow on the host (the reference's own dependency); the GPU library is mandatory: there
 is no CPU fallback.
 """
@@ -203,6 +210,16 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--diversity_levels", type=str, default=None,
                    help="with --diversity: comma-separated cascade levels whose style is rotated (default 5, the paper's choice; a look, "
                         "not a measurement)")
+    # not in the reference: proxy mode, stylise reduced and apply at full size by bilateral grid (include/wct_hip_bgrid.h)
+    p.add_argument("--proxy_scale", type=int, default=None,
+                   help="D in 1 .. 16: stylise the content reduced by D, fit a bilateral grid of local affine colour maps to the reduced pair "
+                        "and apply it to the full content (Chen et al., SIGGRAPH Asia 2016): the content's exact size and edges, colour and "
+                        "tone but no strokes (default: off)")
+    p.add_argument("--proxy_cell", type=int, default=None, help="with --proxy_scale: reduced pixels per grid cell (default 16; a look, not a measurement)")
+    p.add_argument("--proxy_bins", type=int, default=None, help="with --proxy_scale: luminance vertices of the grid, 1 .. 32 (default 8)")
+    p.add_argument("--proxy_eps", type=float, default=None,
+                   help="with --proxy_scale: regulariser of the local fits towards the global one, relative to images in [0, 1] (default 1e-2)")
+    p.add_argument("--proxy_smooth", type=int, default=None, help="with --proxy_scale: [1 2 1] blur passes over the grid's sums, 0 .. 4 (default 1)")
     return p
 
 
@@ -245,6 +262,8 @@ def out_name(args, imname: str, variation: Optional[int] = None) -> str:
     tmark = "_transform=%s" % transform if transform != "wct" else ""                          # directly after alpha; wct names are unchanged
     if getattr(args, "diversity", None):
         tmark += "_div=%g" % args.diversity                                                     # after the transform mark (wct only, so: in its place)
+    if getattr(args, "proxy_scale", None):
+        tmark += "_proxy=%d" % args.proxy_scale                                                 # after the transform mark (mixes with no other mode)
     swap = getattr(args, "swap_level", None)
     if swap:
         tmark += "_swap=%d" % swap                                                              # after the transform mark
@@ -705,6 +724,63 @@ def run_diverse(args, wct, pairs, content_dir, style_dir, logprinter) -> Tuple[f
     return _run_jobs(args, wct, logprinter, jobs), len(jobs)
 
 
+PROXY_FLAGS = (("proxy_cell", "--proxy_cell"), ("proxy_bins", "--proxy_bins"), ("proxy_eps", "--proxy_eps"), ("proxy_smooth", "--proxy_smooth"))
+
+
+def check_proxy_args(args) -> None:
+    """--proxy_scale D and its four parameters: ordinary content x style pairs, one at a time; --alpha, --num_run, --transform,
+    --content_size, --style_size and --round go with it.  The result already carries the content's edges and colours are what it
+    transfers, so the post-steps and every other mode are refused by name.  Fills in the defaults."""
+    from .lib import BGRID_BINS, BGRID_CELL, BGRID_EPS, BGRID_MAX_SMOOTH, BGRID_MAX_Z, BGRID_SMOOTH, SCALE_MAX_DIVISOR
+    D = getattr(args, "proxy_scale", None)
+    if D is None:
+        for attr, name in PROXY_FLAGS:
+            if getattr(args, attr, None) is not None:
+                raise ValueError("%s does nothing without --proxy_scale" % name)
+        return
+    if not 1 <= D <= SCALE_MAX_DIVISOR:
+        raise ValueError("--proxy_scale: a divisor in 1 .. %d expected, got %r" % (SCALE_MAX_DIVISOR, D))
+    clash = [name for flag, name in ((args.synthesis, "--synthesis"), (args.maskPath is not None, "--maskPath"),
+                                     (args.interp_styles is not None, "--interp_styles"), (args.weightPath is not None, "--weightPath"),
+                                     (getattr(args, "video", False), "--video"), (getattr(args, "swap_level", None), "--swap_level"),
+                                     (getattr(args, "level_scale", None), "--level_scale"), (getattr(args, "auto_regions", None), "--auto_regions"),
+                                     (getattr(args, "diversity", None), "--diversity"),
+                                     (getattr(args, "preserve_color", None), "--preserve_color"),
+                                     (getattr(args, "smooth_radius", 0), "--smooth_radius")) if flag]
+    if clash:
+        raise ValueError("--proxy_scale does not mix with %s" % ", ".join(clash))
+    for attr, default in (("proxy_cell", BGRID_CELL), ("proxy_bins", BGRID_BINS), ("proxy_eps", BGRID_EPS), ("proxy_smooth", BGRID_SMOOTH)):
+        if getattr(args, attr, None) is None:
+            setattr(args, attr, default)
+    if args.proxy_cell < 1:
+        raise ValueError("--proxy_cell: a cell of 1 reduced pixel at least expected, got %r" % (args.proxy_cell,))
+    if not 1 <= args.proxy_bins <= BGRID_MAX_Z:
+        raise ValueError("--proxy_bins: 1 .. %d expected, got %r" % (BGRID_MAX_Z, args.proxy_bins))
+    if not 0.0 < args.proxy_eps < float("inf"):              # a NaN fails both comparisons
+        raise ValueError("--proxy_eps: a finite value > 0 expected, got %r" % (args.proxy_eps,))
+    if not 0 <= args.proxy_smooth <= BGRID_MAX_SMOOTH:
+        raise ValueError("--proxy_smooth: 0 .. %d expected, got %r" % (BGRID_MAX_SMOOTH, args.proxy_smooth))
+
+
+def run_proxy(args, wct, pairs, content_dir, style_dir, logprinter) -> Tuple[float, int]:
+    """--proxy_scale: the reference's loop with wct_stylize_proxy in the cascade's place, one pair at a time; the uint8 conversion is
+    fused into the slice.  Returns (total seconds, pairs)."""
+    on_device = _device_images(8)
+
+    def stylise(c_f32, s_u8):
+        return _recompute_fp32(wct, logprinter, "pair", lambda fresh: wct.stylize_proxy(
+            c_f32, _to_tensor(wct, s_u8, args.style_size), args.proxy_scale, args.proxy_cell, args.proxy_bins, args.proxy_eps, args.proxy_smooth,
+            args.alpha, args.num_run, u8=True, round_mode=args.round_mode))
+
+    def job(i, cfile, sfile):
+        imname = pair_name(cfile, sfile)
+        return Job(' #%s: Transferring "%s" (proxy: divisor %d, cell %d, %d bins, eps %g, smooth %d)' % (
+                       i, imname, args.proxy_scale, args.proxy_cell, args.proxy_bins, args.proxy_eps, args.proxy_smooth),
+                   os.path.join(content_dir, cfile), lambda c_u8: on_device(os.path.join(style_dir, sfile)), stylise, out_name(args, imname))
+
+    return _run_jobs(args, wct, logprinter, [job(i, c, s) for i, (c, s) in enumerate(pairs)]), len(pairs)
+
+
 VIDEO_FLAGS = (("temporal_rate", "--temporal_rate"), ("scene_cut", "--scene_cut"), ("temporal_blend", "--temporal_blend"),
                ("temporal_sigma", "--temporal_sigma"), ("temporal_radius", "--temporal_radius"))
 
@@ -841,6 +917,8 @@ def _finish_u8(wct, args, res, c_f32):
     --smooth_radius, then the luminance merge of --preserve_color luma, both against the content tensor the cascade was given."""
     luma = getattr(args, "preserve_color", None) == "luma"
     radius = getattr(args, "smooth_radius", 0)
+    if getattr(args, "proxy_scale", None):
+        return res          # the slice of --proxy_scale has converted it already (it goes with neither post-step)
     if radius:
         if not luma:
             return wct.guided_filter(res, c_f32, radius, args.smooth_eps, u8=True, round_mode=args.round_mode)
@@ -1380,9 +1458,14 @@ DIVERSE_MODE = Mode("diverse", lambda a: getattr(a, "diversity", None), "--diver
                     pair_jobs, True, _number_of("content-style pairs"), "image", run_diverse)
 
 
+# --proxy_scale mixes with none of the above (check_proxy_args): like --diversity it is looked at behind the table
+PROXY_MODE = Mode("proxy", lambda a: getattr(a, "proxy_scale", None), "--proxy_scale: proxy runs use the serial loop",
+                  pair_jobs, True, _number_of("content-style pairs"), "pair", run_proxy)
+
+
 def select_mode(args) -> Optional[Mode]:
-    """The first mode of MODES that `args` choose, then --diversity; None for a plain content x style run."""
-    return next((m for m in MODES + (DIVERSE_MODE,) if m.chosen(args)), None)
+    """The first mode of MODES that `args` choose, then --diversity, then --proxy_scale; None for a plain content x style run."""
+    return next((m for m in MODES + (DIVERSE_MODE, PROXY_MODE) if m.chosen(args)), None)
 
 
 def main(argv: Optional[List[str]] = None) -> int:
@@ -1400,6 +1483,7 @@ def main(argv: Optional[List[str]] = None) -> int:
     check_video_args(args)
     check_motion_args(args)
     check_diverse_args(args)
+    check_proxy_args(args)
     os.makedirs(args.outf, exist_ok=True)
     logprinter = LogPrinter(args.debug, os.path.join(args.outf, "log_%s_%s.txt" % (args.log_mark, args.mode)))
     logprinter(sorted(vars(args).items()))

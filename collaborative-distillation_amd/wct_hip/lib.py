@@ -96,6 +96,12 @@ SYMBOLS_DIVERSE = ["wct_rotation_make", "wct_style_diversify", "wct_stylize_dive
 DIVERSE_MAX_STRENGTH = 8                                            # WCT_DIVERSE_MAX_STRENGTH
 DIVERSE_LEVELS = (5,)                                               # the command line's default --diversity_levels
 
+# every symbol include/wct_hip_bgrid.h declares (proxy mode: stylise reduced, apply at full size by bilateral grid); bound from the same libwct_hip.so
+SYMBOLS_BGRID = ["wct_bgrid_shape", "wct_bgrid_fit", "wct_bgrid_slice", "wct_stylize_proxy"]
+BGRID_MAX_XY, BGRID_MAX_Z, BGRID_MAX_SMOOTH = 256, 32, 4            # WCT_BGRID_MAX_*
+BGRID_FIT_ROWS, BGRID_TILE_W, BGRID_TILE_H, BGRID_LDS_VERTICES = 64, 128, 8, 320   # WCT_BGRID_FIT_ROWS, WCT_BGRID_TILE_*, WCT_BGRID_LDS_VERTICES
+BGRID_CELL, BGRID_BINS, BGRID_EPS, BGRID_SMOOTH = 16, 8, 1e-2, 1    # WCT_BGRID_*: the command line's defaults
+
 
 class WctLayer(ctypes.Structure):
     _fields_ = [("cin", c_int), ("cout", c_int), ("pool_after", c_int), ("up_after", c_int),
@@ -270,6 +276,10 @@ def load() -> ctypes.CDLL:
     lib.wct_style_diversify.argtypes = [c_void_p, ctypes.c_uint, c_double, ctypes.c_uint64, ctypes.c_uint32]
     lib.wct_stylize_diverse.argtypes = [c_void_p, vp, c_int, c_int, vp, c_int, c_int, ctypes.c_uint, c_double, ctypes.c_uint64, ctypes.c_uint32, c_float, c_int,
                                         vp, ip, ip]
+    lib.wct_bgrid_shape.argtypes = [c_int, c_int, c_int, ip, ip]
+    lib.wct_bgrid_fit.argtypes = [c_void_p, vp, vp, c_int, c_int, c_int, c_int, c_int, c_double, c_int, vp]
+    lib.wct_bgrid_slice.argtypes = [c_void_p, vp, c_int, c_int, c_int, vp, c_int, c_int, vp, vp, c_int]
+    lib.wct_stylize_proxy.argtypes = [c_void_p, vp, c_int, c_int, vp, c_int, c_int, c_float, c_int, c_int, c_int, c_int, c_double, c_int, vp, vp, c_int]
     lib.wct_set_transform.argtypes = [c_void_p, c_int]
     lib.wct_get_transform.argtypes = [c_void_p, ip]
     lib.wct_transform_solve.argtypes = [c_void_p, c_int, c_int, c_double, vp, vp, vp, c_double, vp, vp, ip]

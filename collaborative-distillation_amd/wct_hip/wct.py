@@ -1258,6 +1258,100 @@ class WCT:
             self._style_keep = s      # the side stream reads it asynchronously
         return out.view(-1)[: 3 * ho.value * wo.value].view(1, 3, ho.value, wo.value)
 
+    # ------------------------------------------------------------------ proxy mode (include/wct_hip_bgrid.h)
+    @staticmethod
+    def bgrid_shape(h: int, w: int, cell: int = _lib.BGRID_CELL):
+        """(gh, gw) = (ceil(h / cell) + 1, ceil(w / cell) + 1): the spatial vertices of a bilateral grid over an h x w image
+        (wct_bgrid_shape, host only).  ValueError for an empty shape, cell < 1 or a result above 256."""
+        gh, gw = c_int(), c_int()
+        if _lib.load().wct_bgrid_shape(int(h), int(w), int(cell), byref(gh), byref(gw)) != _lib.WCT_OK:
+            raise ValueError("bgrid_shape: %d x %d with cell %r: a non-empty shape, cell >= 1 and at most %d vertices per axis expected"
+                             % (h, w, cell, _lib.BGRID_MAX_XY))
+        return gh.value, gw.value
+
+    @staticmethod
+    def _bgrid_args(what: str, gz=None, gh=None, gw=None, eps=None, smooth=None) -> None:
+        for name, g, top in (("gz", gz, _lib.BGRID_MAX_Z), ("gh", gh, _lib.BGRID_MAX_XY), ("gw", gw, _lib.BGRID_MAX_XY)):
+            if g is not None and (int(g) != g or not 1 <= int(g) <= top):
+                raise ValueError("%s: %s must be an integer in 1 .. %d, got %r" % (what, name, top, g))
+        if eps is not None and not (float(eps) > 0.0 and float(eps) < float("inf")):
+            raise ValueError("%s: eps must be finite and positive, got %r" % (what, eps))
+        if smooth is not None and (int(smooth) != smooth or not 0 <= int(smooth) <= _lib.BGRID_MAX_SMOOTH):
+            raise ValueError("%s: smooth must be an integer in 0 .. %d, got %r" % (what, _lib.BGRID_MAX_SMOOTH, smooth))
+
+    @torch.no_grad()
+    def bgrid_fit(self, reduced: torch.Tensor, stylised: torch.Tensor, gz: int, gh: int, gw: int, eps: float = _lib.BGRID_EPS,
+                  smooth: int = _lib.BGRID_SMOOTH, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The bilateral grid of local 3 x 4 affine colour maps that takes `reduced` to `stylised` (two images of one size): an fp32
+        tensor [gz, gh, gw, 3, 4] (wct_bgrid_fit; Chen et al. 2016).  Weighted least squares per vertex, regularised towards the
+        global fit by `eps`, the sums blurred `smooth` times; fp64 inside, rounded once; bitwise reproducible."""
+        a, b = self._img(reduced), self._img(stylised)
+        if tuple(a.shape) != tuple(b.shape):
+            raise ValueError("bgrid_fit: the two images must have one shape, got %s and %s" % (tuple(a.shape), tuple(b.shape)))
+        self._bgrid_args("bgrid_fit", gz, gh, gw, eps, smooth)
+        h, w = int(a.shape[1]), int(a.shape[2])
+        out = self._out_like(out, "bgrid_fit", int(gz) * int(gh) * int(gw) * 12)
+        if out is None:
+            out = torch.empty((int(gz), int(gh), int(gw), 3, 4), device=a.device, dtype=torch.float32)
+        self._stream()
+        self._chk(self._lib.wct_bgrid_fit(self._ctx, a.data_ptr(), b.data_ptr(), h, w, int(gz), int(gh), int(gw), float(eps), int(smooth),
+                                          out.data_ptr()))
+        return out.view(int(gz), int(gh), int(gw), 3, 4)
+
+    @torch.no_grad()
+    def bgrid_slice(self, grid: torch.Tensor, content: torch.Tensor, out: Optional[torch.Tensor] = None, u8: bool = False,
+                    round_mode: int = 0) -> torch.Tensor:
+        """The grid [gz, gh, gw, 3, 4] applied to a full-resolution image: per pixel the affine map interpolated from its 8 vertices
+        (x, y, and the pixel's own luminance), evaluated in fp64, not clamped (wct_bgrid_slice).  u8=False: fp32 [1,3,H,W], `out`
+        may be `content` itself; u8=True: uint8 [H,W,3] with the conversion of to_u8(., round_mode) fused in, byte-identical to
+        to_u8 of the fp32 result."""
+        if grid.dim() != 5 or tuple(grid.shape[3:]) != (3, 4):
+            raise ValueError("bgrid_slice: expected a [gz, gh, gw, 3, 4] grid, got %s" % (tuple(grid.shape),))
+        gz, gh, gw = int(grid.shape[0]), int(grid.shape[1]), int(grid.shape[2])
+        self._bgrid_args("bgrid_slice", gz, gh, gw)
+        g, c = self._dev_f32(grid), self._img(content)
+        H, W = int(c.shape[1]), int(c.shape[2])
+        out = self._out_like(out, "bgrid_slice", 3 * H * W, torch.uint8 if u8 else torch.float32)
+        if out is None:
+            out = torch.empty((H, W, 3), device=c.device, dtype=torch.uint8) if u8 else \
+                torch.empty((1, 3, H, W), device=c.device, dtype=torch.float32)
+        self._stream()
+        self._chk(self._lib.wct_bgrid_slice(self._ctx, g.data_ptr(), gz, gh, gw, c.data_ptr(), H, W, None if u8 else out.data_ptr(),
+                                            out.data_ptr() if u8 else None, int(round_mode)))
+        return out.view(H, W, 3) if u8 else out.view(1, 3, H, W)
+
+    @torch.no_grad()
+    def stylize_proxy(self, contentImg: torch.Tensor, styleImg: Optional[torch.Tensor], divisor: int, cell: int = _lib.BGRID_CELL,
+                      bins: int = _lib.BGRID_BINS, eps: float = _lib.BGRID_EPS, smooth: int = _lib.BGRID_SMOOTH, alpha: Optional[float] = None,
+                      num_run: int = 1, out: Optional[torch.Tensor] = None, u8: bool = False, round_mode: int = 0) -> torch.Tensor:
+        """Proxy mode, one library call (wct_stylize_proxy): the content reduced to scale_shape(H, W, divisor), stylised there, a
+        bilateral grid (bgrid_shape(., cell) x `bins` luminance vertices) fitted to the reduced pair and applied to the FULL content.
+        The result has the content's exact H x W and its edges -- colour and tone, no strokes.  Bit-identical to the composition of
+        resample / stylize / bgrid_fit / bgrid_slice.  styleImg=None runs against the statistics already in the context."""
+        if int(divisor) != divisor or not 1 <= int(divisor) <= _lib.SCALE_MAX_DIVISOR:
+            raise ValueError("stylize_proxy: divisor must be an integer in 1 .. %d, got %r" % (_lib.SCALE_MAX_DIVISOR, divisor))
+        self._bgrid_args("stylize_proxy", gz=bins, eps=eps, smooth=smooth)
+        alpha = self.alpha if alpha is None else float(alpha)
+        c = self._img(contentImg)
+        H, W = int(c.shape[1]), int(c.shape[2])
+        h, w = self.scale_shape(H, W, int(divisor))
+        self.bgrid_shape(h, w, cell)
+        s, Hs, Ws = None, 0, 0
+        if styleImg is not None:
+            s = self._img(styleImg)
+            Hs, Ws = int(s.shape[1]), int(s.shape[2])
+        out = self._out_like(out, "stylize_proxy", 3 * H * W, torch.uint8 if u8 else torch.float32)
+        if out is None:
+            out = torch.empty((H, W, 3), device=c.device, dtype=torch.uint8) if u8 else \
+                torch.empty((1, 3, H, W), device=c.device, dtype=torch.float32)
+        self._stream()
+        self._chk(self._lib.wct_stylize_proxy(self._ctx, c.data_ptr(), H, W, s.data_ptr() if s is not None else None, Hs, Ws, alpha, int(num_run),
+                                              int(divisor), int(cell), int(bins), float(eps), int(smooth), None if u8 else out.data_ptr(),
+                                              out.data_ptr() if u8 else None, int(round_mode)))
+        if s is not None:
+            self._style_keep = s      # the side stream reads it asynchronously
+        return out.view(H, W, 3) if u8 else out.view(1, 3, H, W)
+
     # ------------------------------------------------------------------ video mode (include/wct_hip_video.h)
     def clip(self, H: int, W: int, rate: float = _lib.CLIP_RATE, cut: float = _lib.CLIP_CUT, blend: float = _lib.CLIP_BLEND,
              sigma: float = _lib.CLIP_SIGMA, radius: int = _lib.CLIP_RADIUS, motion=None) -> "Clip":
