@@ -1,5 +1,6 @@
 """Attention statistics without a GPU: the public header and its bindings, identities of the numpy reference (tests/attn_oracle.py), the
-command line's --swap_match attention / --swap_temp, and the input condition of the GPU level tests."""
+command line's --swap_match attention / --swap_temp, the input condition of the GPU level tests, and the launch plan and the edge cases of
+tests/test_attn_edges_gpu.py (tests/attn_cases.py): the plan against the source, and that every planted case separates a wrong kernel."""
 import os
 import re
 import subprocess
@@ -10,7 +11,10 @@ import pytest
 
 from tests import attn_cases as AC
 from tests import attn_oracle as A
+from tests import sweep_cases
+from tests import width_models as wm
 from tests.conftest import PKG, REPO
+from tests.test_attn_gpu import FLOOR_MEAN, FLOOR_VAR
 from wct_hip import cli, lib
 
 HEADER = os.path.join(REPO, "include", "wct_hip_attn.h")
@@ -156,6 +160,178 @@ def test_the_gpu_level_cases_meet_the_input_condition(model, level, domain):
     assert live.any()
     print("%s level %d domain %d: min var over %d live channels %.3e" % (model, level, domain, int(live.sum()), var[:, live].min()))
     assert var[:, live].min() >= AC.MIN_VAR
+
+
+@pytest.mark.parametrize("model,level,domain", AC.EDGE_LEVEL_CASES)
+def test_the_gpu_edge_level_cases_meet_the_input_condition(model, level, domain):
+    """The same statement for the level cases of tests/test_attn_edges_gpu.py (E8): level 3 at C = 256 and at C = 132.  The stand-in model
+    is one wct_load_module takes, every module of it."""
+    widths = AC.ALL_LEVEL_MODELS[model][0]
+    for lv in (1, 2, 3, 4, 5):
+        assert wm.loadable("enc", wm.encoder_layers(widths, lv)) and wm.loadable("dec", wm.decoder_layers(widths, lv)), (model, lv)
+    cF, sF = AC.level_features(model, level)
+    assert cF.shape[-1] == widths[3] == {"wide": 256, "w132": 132}[model]
+    _, _, var = AC.level_reference(model, level, domain)
+    live = A.live_channels(sF)
+    assert live.any()
+    print("%s level %d domain %d: min var over %d live channels %.3e" % (model, level, domain, int(live.sum()), var[:, live].min()))
+    assert var[:, live].min() >= AC.MIN_VAR
+
+
+# ---------------------------------------------------------------------------------------------------------------- the launch plan and the edge cases
+def gates(e32):
+    """The gate of wct_attn_stats (tests/test_attn_gpu.py) for a case whose fp32 arm is at e32 = (mean, var)."""
+    return 4 * e32[0] + FLOOR_MEAN, 4 * e32[1] + FLOOR_VAR
+
+
+def test_the_plan_constants_are_the_kernel_s():
+    src = open(os.path.join(PKG, "csrc", "attn.hip")).read()
+    api = open(os.path.join(PKG, "csrc", "api_attn.hip")).read()
+    header = open(HEADER).read()
+    m = re.search(r"constexpr int AT_QT = (\d+), AT_KT = (\d+), AT_CS = (\d+)", src)
+    assert m and int(m.group(3)) == AC.VALUE_SLAB
+    m = re.search(r"#define WCT_ATTN_QUERY_CHUNK\s+(\d+)", header)
+    assert m and int(m.group(1)) == AC.QUERY_CHUNK == lib.ATTN_QUERY_CHUNK and AC.QUERY_CHUNK % AC.QUERY_TILE == 0
+    assert "ctx->attn_query_chunk > 0 ? ctx->attn_query_chunk : WCT_ATTN_QUERY_CHUNK" in api
+    assert '"%s"' % AC.PROFILE_NAME in api and '"l%d.s%u", nlaunch, slabs' in src
+    # the expressions `plan` restates
+    for text in ("(C + AT_CS - 1) / AT_CS", "(e - b + AT_QT - 1) / AT_QT", "((long)Nk + AT_KT - 1) / AT_KT", "const int nct = (slabC + 15) >> 4;",
+                 "const int nks = cleft >= 128 ? 4 : (cleft + 31) >> 5;", "if (c + 4 < C) b ="):
+        assert text in src, text
+    m = re.search(r"constexpr int AW_PIX = (\d+);", src)
+    assert m and int(m.group(1)) == AC.WHITEN_PIX
+    assert AC.WIDTHS == sweep_cases.WIDTHS and len(AC.WIDTHS) == 128
+
+
+def test_the_plan_on_worked_cases():
+    P = AC.plan
+    assert P(65, 33, 4) == AC.Plan(1, 1, (2,), 2, 1, 1, True, "l1.s1")
+    assert P(64, 32, 128) == AC.Plan(1, 1, (1,), 1, 8, 4, False, "l1.s1")
+    assert P(65, 33, 132) == AC.Plan(1, 2, (2,), 2, 1, 1, True, "l1.s2")
+    assert P(2, 2, 256) == AC.Plan(1, 2, (1,), 1, 8, 4, False, "l1.s2")
+    assert P(70, 129, 360) == AC.Plan(1, 3, (2,), 5, 7, 4, False, "l1.s3")          # 104 channels left: 6.5 value tiles, 3.25 score steps
+    assert P(70, 129, 388) == AC.Plan(1, 4, (2,), 5, 1, 1, True, "l1.s4")
+    assert P(AC.SPLIT_NQ, 33, 132) == AC.Plan(2, 2, (512, 2), 2, 1, 1, True, "l2.s2")
+    assert P(AC.SPLIT_NQ, 33, 4).form == "l2.s1" and P(AC.QUERY_CHUNK, 33, 4).form == "l1.s1"
+    assert P(203, 378, 36, chunk=50) == AC.Plan(5, 1, (1, 1, 1, 1, 1), 12, 3, 2, True, "l5.s1")
+    assert AC.profile_name(65, 33, 512) == "attn_stats<f16x3>:l1.s4"
+
+
+def test_the_case_lists_reach_every_tail_class():
+    """(nct of the last slab, nks of the last chunk, half-live last group): 16 classes over the 128 widths.  The bands of E1 hold every
+    width; the planted list of E2 must be shown to hold every class, in one slab and in several."""
+    every = {AC.tail_class(C) for C in AC.WIDTHS}
+    assert len(every) == 16 and every == {(n, (n + 1) // 2, h) for n in range(1, 9) for h in (False, True)}
+    assert sorted(C for b in sweep_cases.BANDS for C in b) == list(AC.WIDTHS)
+    assert {AC.tail_class(C) for C in AC.PLANT_WIDTHS} == every
+    assert {AC.tail_class(C) for C in AC.PLANT_WIDTHS if C > 128} == every
+    named = (4, 8, 12, 20, 28, 36, 100, 124, 132, 136, 156, 252, 256, 260, 264, 380, 388, 508, 512)
+    assert AC.PLANT_WIDTHS[:len(named)] == named and len(set(AC.PLANT_WIDTHS)) == len(AC.PLANT_WIDTHS)
+    assert {AC.plan(2, 2, C).slabs for C in AC.ROLL_WIDTHS} == {2, 3, 4} and all(r % 4 == 0 for r in AC.ROLLS)
+    assert AC.plants(4) == {"last4": 0} and AC.plants(12) == {"last4": 8, "hi_half": 4} and AC.plants(136) == {"last4": 132, "chunk_first": 128}
+    assert AC.plants(132) == {"last4": 128, "hi_half": 124} and AC.plants(260) == {"last4": 256, "hi_half": 252}
+    assert AC.plants(264) == {"last4": 260, "chunk_first": 256}
+
+
+@pytest.mark.parametrize("C", AC.PLANT_WIDTHS)
+def test_e2_the_planted_group_decides(C):
+    """Zeroing the planted group in k^ moves the fp64 mean by at least 0.1 max |V|: a staging that drops, zero-fills or misplaces those four
+    channels cannot pass a gate of 5e-6."""
+    q0, k0, v0 = AC.edge_inputs(C)
+    for name, c0 in AC.plants(C).items():
+        q, k, v = AC.planted_inputs(C, c0)
+        assert q.dtype == np.float32 and np.abs((q.astype(np.float64) ** 2).sum(1) - 1).max() < 1e-6 and np.array_equal(v, v0)
+        share = (k.astype(np.float64)[:, c0:c0 + 4] ** 2).sum(1)
+        (m64, _), e32, vmax = AC.reference(q, k, v, AC.PLANT_TAU)
+        cut = np.array(k)
+        cut[:, c0:c0 + 4] = 0
+        moved = np.abs(A.stats(q, cut, v, AC.PLANT_TAU)[0] - m64).max() / vmax
+        print("E2 C=%d %s (channels %d..%d): median share of |k^|^2 %.2f, zeroing moves the mean by %.3f max|V|; gate %.2e / %.2e"
+              % (C, name, c0, c0 + 3, np.median(share), moved, *gates(e32)))
+        assert moved >= 0.1, (C, name, moved)
+
+
+def test_e4_the_standardised_key_subsets_have_the_header_s_tau_zero_statistics():
+    for C in AC.BORDER_WIDTHS:
+        for Nk in AC.BORDER_NK:
+            v, want = AC.border_standardised(C, Nk)
+            q, k, _ = AC.border_inputs(C, 65, Nk)
+            m64, v64 = A.stats(q, k, v, 0.0)
+            vmax = np.abs(v).max()
+            assert np.abs(m64).max() / vmax < 1e-7 and np.abs(v64 - want).max() / vmax ** 2 < 1e-6, (C, Nk)      # V rounded to fp32 once
+
+
+@pytest.mark.parametrize("C", AC.RUN_WIDTHS)
+def test_e5_the_key_orders_drive_the_running_maximum(C):
+    """Ascending: every query's per-tile maximum strictly increases over all five tiles; descending (and "own"): never after tile 0.  In
+    "own" every key but the first is at least 1.69 tau below it: P' = 2^15 e^(-54) rounds to 0 in f16 (smallest subnormal 6e-8)."""
+    for order in AC.RUN_ORDERS:
+        q, k, v = AC.running_inputs(C, order)
+        assert q.shape == (AC.RUN_NQ, C) and k.shape == v.shape == (AC.RUN_NK, C) and AC.plan(AC.RUN_NQ, AC.RUN_NK, C).key_tiles == 5
+        assert np.abs((k.astype(np.float64) ** 2).sum(1) - 1).max() < 1e-6
+        tm = AC.tile_maxima(q, k, AC.RUN_TAU)
+        assert tm.shape == (AC.RUN_NQ, 5)
+        if order.endswith("up"):
+            assert (np.diff(tm, axis=1) > 0).all(), order
+            print("E5 C=%d %s: smallest / largest step of a tile maximum %.3f / %.3f" % (C, order, np.diff(tm, axis=1).min(), np.diff(tm, axis=1).max()))
+        else:
+            assert (tm[:, 1:] < tm[:, :1]).all(), order
+    sets = [sorted(map(bytes, AC.running_inputs(C, o)[1])) for o in ("up", "down", "own")]
+    assert sets[0] == sets[1] == sets[2], "one key set in three orders"
+    q, k, v = AC.running_inputs(C, "own")
+    s = AC.RUN_TAU * (q.astype(np.float64) @ k.astype(np.float64).T)
+    assert (s[:, 1:].max(1) - s[:, 0] <= -1.69 * AC.RUN_TAU).all() and 2.0 ** 15 * np.exp(-1.69 * AC.RUN_TAU) < 2.0 ** -25
+    m64, v64 = A.stats(q, k, v, AC.RUN_TAU)
+    assert np.abs(m64 - v[0]).max() < 1e-12 and v64.max() < 1e-12
+    drop = np.exp(s[:, 1:] - s[:, :1]).sum(1).max()
+    assert drop <= AC.RUN_NK * 2.0 ** -40                                      # the header's bound on the weight mass a conversion may drop
+
+
+def test_e5_the_online_walk_is_the_oracle_and_its_mutants_are_not():
+    """online_stats is attn_oracle.stats to 1e-12.  The walk that never rescales differs from fp64 by at least 100 gates on the ascending
+    orders; the walk that counts the pad keys of the last tile differs by at least 100 gates on E4's Nk = 33 at tau = 0 (where a pad key
+    has the weight of a key; at tau = 32 its score 0 lies 10 and more below the maximum)."""
+    for C in AC.RUN_WIDTHS:
+        for order in AC.RUN_ORDERS:
+            q, k, v = AC.running_inputs(C, order)
+            (m64, v64), e32, vmax = AC.reference(q, k, v, AC.RUN_TAU)
+            gm, gv = gates(e32)
+            m, var = AC.online_stats(q, k, v, AC.RUN_TAU)
+            assert np.abs(m - m64).max() < 1e-12 and np.abs(var - v64).max() < 1e-12
+            m, var = AC.online_stats(q, k, v, AC.RUN_TAU, rescale=False)
+            dm, dv = np.abs(m - m64).max() / vmax, np.abs(var - v64).max() / vmax ** 2
+            print("E5 C=%d %s: never rescaling is off by %.2e / %.2e (gates %.2e / %.2e)" % (C, order, dm, dv, gm, gv))
+            if order.endswith("up"):
+                assert dm >= 100 * gm and dv >= 100 * gv, (C, order, dm, dv)
+            else:
+                assert dm < 1e-12 and dv < 1e-12                              # nothing to rescale: why the ascending orders are needed
+    for C in AC.BORDER_WIDTHS:
+        q, k, v = AC.border_inputs(C, 65, 33)
+        (m64, v64), e32, vmax = AC.reference(q, k, v, 0.0)
+        gm, gv = gates(e32)
+        m, var = AC.online_stats(q, k, v, 0.0)
+        assert np.abs(m - m64).max() < 1e-12 and np.abs(var - v64).max() < 1e-12
+        m, var = AC.online_stats(q, k, v, 0.0, count_pad=True)
+        dm, dv = np.abs(m - m64).max() / vmax, np.abs(var - v64).max() / vmax ** 2
+        print("E4 C=%d Nk=33 tau=0: counting the 31 pad keys is off by %.2e / %.2e (gates %.2e / %.2e)" % (C, dm, dv, gm, gv))
+        assert dm >= 100 * gm and dv >= 100 * gv, (C, dm, dv)
+
+
+#: 2^-53 cond moves cov^(-1/2) by a tenth of the 1e-8 solve gate at cond = 9e6 (tests/test_sweep_gpu.py SOLVE_MAX_COND): far inside the 1e-6
+#: of the projection, so a map below it is held to the ordinary gate and one above it would be replaced here
+WHITEN_MAX_COND = 1e-9 / 2.0 ** -53
+
+
+@pytest.mark.parametrize("C", AC.WHITEN_WIDTHS)
+def test_e7_the_whitened_maps_are_well_conditioned(C):
+    f = AC.whiten_map(C)
+    n = f.shape[0] * f.shape[1]
+    assert n == 2 * C + 3 and n % AC.WHITEN_PIX != 0
+    lam = np.linalg.eigvalsh(np.cov(np.asarray(f, np.float64).reshape(n, C).T))
+    print("E7 C=%d: %d positions, cond(cov) = %.3e" % (C, n, lam[-1] / lam[0]))
+    assert lam[0] > 0 and lam[-1] / lam[0] <= WHITEN_MAX_COND
+    u64, _ = A.project(f, A.WHITENED)
+    assert np.isfinite(u64).all() and np.abs((u64 ** 2).sum(-1) - 1).max() < 1e-9
 
 
 # ---------------------------------------------------------------------------------------------------------------- command line
