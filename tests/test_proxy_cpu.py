@@ -110,6 +110,104 @@ def test_gated_cases_are_well_conditioned():
     assert G.GRIDS["fine"][2:] == (4, 9, 9) and 4 * 9 * 9 > lib.BGRID_LDS_VERTICES >= 4 * 8 * 9
 
 
+# ---------------------------------------------------------------------------------------------------------------- the edge cases
+def test_edge_fit_cases_are_well_conditioned():
+    """The condition of test_gated_cases_are_well_conditioned for every case of tests/proxy_edge_cases.py.  If an image or a seed ever
+    breaks it, the case changes, never the bound."""
+    from tests import proxy_edge_cases as E
+    assert len(E.EDGE_FIT_CASES) == 6 * len(E.EDGE_FIT_SHAPES) and set(c[6:] for c in E.EDGE_FIT_CASES) == {(e, s) for e in (1e-2, 1e-4) for s in (0, 1, 4)}
+    assert len(set(E.EDGE_FIT_CASES)) == len(E.EDGE_FIT_CASES)
+    assert set(E.POISON_CASES) | set(E.UNREACHED) <= set(E.EDGE_FIT_CASES)
+    worst_a, worst_c = (0.0, None), (0.0, None)
+    for case in E.EDGE_FIT_CASES:
+        _, _, A, _, cond = E.fit_reference(*case)
+        a = float(np.abs(A).max())
+        worst_a, worst_c = max(worst_a, (a, case)), max(worst_c, (cond, case))
+        assert np.isfinite(A).all() and a <= 4.0 and cond <= 1e6, (case, a, cond)
+    print("edge fit cases: worst max |A| = %.3f at %s, worst cond = %.3e at %s" % (worst_a[0], E.fit_id(worst_a[1]), worst_c[0], E.fit_id(worst_c[1])))
+
+
+def test_wide_images_leave_the_unit_range_and_reach_both_ends_of_the_guide():
+    from tests import proxy_edge_cases as E
+    wide = [E.fit_images(h, w, kind)[0] for h, w, _, _, _, kind, _ in E.EDGE_FIT_SHAPES if kind == "wide"] + \
+           [E.slice_image(H, W, kind) for _, _, _, H, W, kind, _ in E.EDGE_SLICE_CASES if kind == "wide"]
+    assert len(wide) == 7
+    big = [c for c in wide if c[0].size >= 4]
+    assert len(big) == 6
+    for c in big:
+        g = O.guide(c)
+        assert c.dtype == np.float32 and (g == 0.0).any() and (g == 1.0).any() and c.min() < 0.0 < 1.0 < c.max(), (c.shape, c.min(), c.max())
+        assert [float(v) for v in c.reshape(3, -1)[0, :4]] == [0.0, 1.0, 2.0, -0.5]
+        raw = O.LUMA @ c.reshape(3, -1).astype(np.float64)
+        assert c[0].size < 100 or (raw < 0.0).sum() >= 10 and (raw > 1.0).sum() >= 10, "tens of pixels beyond either end besides the planted ones"
+        print("wide %dx%d: content in [%.3f, %.3f], %d pixels with guide 0, %d with guide 1" % (c.shape[1:] + (c.min(), c.max(), (g == 0).sum(), (g == 1).sum())))
+    assert all(np.isfinite(E.fit_images(h, w, kind)[1]).all() for h, w, _, _, _, kind, _ in E.EDGE_FIT_SHAPES), "the tone curve of a clipped content"
+    # and no image gated before these reaches either end: tests/test_proxy_gpu.py's fit and slice images
+    from tests import test_proxy_gpu as G
+    for img in [G.fit_pair(h, w, narrow)[0] for h, w, _, _, _, narrow, _ in G.FIT_SHAPES] + [G.full_image(H, W) for _, H, W in G.SLICE_CASES]:
+        g = O.guide(img)
+        assert 0.0 < g.min() and g.max() < 1.0
+
+
+def test_edge_cases_reach_the_branches_they_name():
+    """Every count from the header's rule (tests/proxy_edge_cases.py: the oracle's tent, the header's constants), none from the product."""
+    from tests import proxy_edge_cases as E
+    src = open(os.path.join(REPO, "collaborative-distillation_amd", "csrc", "bgrid.hip")).read()
+    assert "constexpr int BG_WX = %d;" % E.TABLE in src and "constexpr int BG_SLAB = %d;" % E.SLAB in src, "the two constants the header does not name"
+    assert (E.ROWS, E.TW, E.TH, E.CAP) == (64, 128, 8, 320)
+    shapes = [s[:5] for s in E.EDGE_FIT_SHAPES]
+    assert len(set(s[:6] for s in E.EDGE_FIT_SHAPES)) == len(shapes)
+    # column supports.  A support that is the whole row cannot be cut more generously: its width is exact.
+    widths = {s: E.support_widths(s[1], s[4]) for s in shapes}
+    whole = {max(ws) for s, ws in widths.items() if max(ws) == s[1]}
+    assert {63, 64, 65, 128, E.TABLE, E.TABLE + 1, 300, 600} <= whole
+    assert widths[(3, 600, 2, 1, 3)] == [300, 600, 300] and widths[(3, 500, 2, 1, 3)] == [250, 500, 250]
+    mixed = [s for s, ws in widths.items() if min(ws) + 2 <= E.TABLE < max(ws) and s[1] > E.TABLE]
+    assert (3, 500, 2, 1, 3) in mixed, "tabulated and untabulated vertices in one launch"
+    assert widths[(100, 1, 2, 3, 1)] == [1] and widths[(2, 1024, 1, 1, 2)] == [1024, 1024]
+    # row chunks: an outer vertex with fewer chunks than an inner one, however generously the support is cut
+    chunks = {s: E.row_chunks(s[0], s[3]) for s in shapes}
+    assert chunks[(200, 7, 2, 3, 2)] == [(2, 2), (4, 4), (2, 2)]
+    assert [c[0] for c in chunks[(193, 5, 3, 4, 1)]] == [1, 3, 3, 1] and [c[1] for c in chunks[(193, 5, 3, 4, 1)]] == [2, 3, 3, 2]
+    spans = E.vertex_spans(193, 4)
+    assert spans[2][0] % E.ROWS != 0 or spans[3][0] % E.ROWS != 0, "a support starts inside a chunk of the image's rows"
+    ragged = [s for s, c in chunks.items() if len(c) >= 3 and max(c[0][1], c[-1][1]) < max(lo for lo, _ in c[1:-1])]
+    assert (200, 7, 2, 3, 2) in ragged and (193, 5, 3, 4, 1) in ragged
+    # the totals
+    counts = [E.slabs(*s[2:]) for s in shapes]
+    assert counts.count(64) >= 2 and counts.count(65) == 2 and counts.count(67) == 2 and max(counts) == 67
+    # ... and a lane's second step adds something: vertex (k, j, i) is number (k gh + j) gw + i, so the slabs past the 64th of a grid
+    # with many bins are its brightest bins, which the images of fit_pair leave empty; the two grids of two bins put weight there
+    assert [E.weight_past_slab(24, 24, *g, "fit") for g in ((5, 29, 113), (32, 23, 23))] == [0.0, 0.0]
+    assert E.weight_past_slab(24, 24, 2, 91, 91, "fit") > 1.0 and E.weight_past_slab(24, 24, 2, 92, 92, "fit") > 10.0
+    assert 5 * 29 * 113 == 64 * E.SLAB + 1 and E.slabs(32, 2, 256) == 64 and (32, 40, 32, 2, 256) in shapes and (20, 12, 1, 256, 3) in shapes
+    for case in E.UNREACHED:
+        _, _, A, Ag, _ = E.fit_reference(*case)
+        Gv, _ = O.sums(*E.fit_images(*case[:2], case[5]), *case[2:5])
+        reached = Gv[..., 3, 3] != 0.0
+        assert case[7] == 0 and 0 < reached.sum() < reached.size / 2 and np.abs(A[~reached] - Ag).max() <= 1e-13 and np.abs(A[reached] - Ag).max() > 1e-3
+    # the slice
+    cases = [c[:6] for c in E.EDGE_SLICE_CASES]
+    assert len(set(cases)) == len(cases) == 18
+    assert set(E.MIXED + E.AT_CAP + E.OVER_CAP + E.BITWISE + [E.NONFINITE]) <= set(cases)
+    foot = {c: E.tile_footprints(*c[:5]) for c in cases}
+    for c, f in foot.items():
+        assert len(f) == -(-c[3] // E.TH) * -(-c[4] // E.TW) and min(f) >= c[0] and max(f) <= c[0] * c[1] * c[2], c
+    assert foot[(4, 2, 100, 8, 130, "full")] == [792, 24]
+    f = foot[(4, 20, 100, 17, 258, "full")]
+    assert len(f) == 9 and sum(n > E.CAP for n in f) == 6 and sum(n <= E.CAP for n in f) == 3
+    both = [c for c, f in foot.items() if min(f) <= E.CAP < max(f)]
+    assert set(E.MIXED) <= set(both) and len(E.MIXED) >= 2        # the largest x axis over three tiles mixes the paths too
+    assert all(foot[c] == [E.CAP] for c in E.AT_CAP) and foot[E.OVER_CAP[0]] == [E.CAP + 1] and foot[E.OVER_CAP[1]] == [330]
+    assert len(foot[(8, 5, 7, 1, 1000, "full")]) == 8 and len(foot[(8, 5, 7, 1000, 1, "full")]) == 125
+    for axis in range(3):
+        assert any(c[axis] == 1 and all(c[a] > 1 for a in range(3) if a != axis) for c in cases), axis
+    assert (1, 1, 1) in {c[:3] for c in cases} and {32} <= {c[0] for c in cases} and {256} <= {c[1] for c in cases} & {c[2] for c in cases}
+    assert {c[4] % 4 for c in cases} >= {1, 2} and any(c[4] < 4 and c[4] > 1 for c in cases)
+    grid = E.random_grid(8, 5, 7)
+    assert grid.dtype == np.float32 and -0.3 <= grid.min() < -0.25 and 0.65 < grid.max() < 0.7
+
+
 # ---------------------------------------------------------------------------------------------------------------- header and bindings
 def declared():
     return sorted(set(re.findall(r"\b(wct_[a-z_0-9]+)\s*\(", open(HEADER).read())) - {"wct_ctx"})

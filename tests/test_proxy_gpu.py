@@ -68,10 +68,16 @@ def fit_pair(h, w, narrow=False):
     c = q8(CO.natural(h * 7 + w, h, w))
     if narrow:
         c = q8(0.4 + 0.2 * c.astype(np.float64))
+    return c, tone_curve(c)
+
+
+def tone_curve(c):
+    """fit_pair's "stylisation" of a 3 x h x w content with values >= 0 (tests/proxy_edge_cases.py feeds it a clipped wide-range one)."""
+    h, w = c.shape[1:]
     x = c.astype(np.float64)
     mix = np.array([[0.7, 0.3, -0.1], [0.1, 0.8, 0.2], [-0.2, 0.3, 0.9]])
     s = np.einsum("ci,ihw->chw", mix, np.sqrt(x)) * 1.1 - 0.1 + 0.15 * CO.natural(h * 13 + w + 1, h, w, cast=(0.6, 1.0, 0.9), shift=(0.2, 0.0, 0.1))
-    return c, s.astype(np.float32)
+    return s.astype(np.float32)
 
 
 # (h, w, gz, gh, gw, narrow, why): the issue's seven, the fit's row-chunk edges (a support is the whole image with gh <= 2), the empty bins
@@ -198,8 +204,12 @@ def test_slice_against_the_oracle_and_between_its_two_paths(torch, wct, name, H,
 
 @pytest.mark.parametrize("name,H,W", [("40x56", 37, 53), ("40x56", 130, 257), ("16x16", TH + 1, TW + 1), ("fine", 8, 8)])
 def test_slice_bitwise_properties(torch, wct, name, H, W):
-    grid = device_grid(torch, wct, name)
-    x = cu(torch, full_image(H, W))
+    slice_bitwise_properties(torch, wct, device_grid(torch, wct, name), cu(torch, full_image(H, W)))
+
+
+def slice_bitwise_properties(torch, wct, grid, x):
+    """The bitwise properties of one slice of the device image x [3, H, W] (tests/test_proxy_edges_gpu.py runs them at its own shapes)."""
+    H, W = int(x.shape[1]), int(x.shape[2])
     got = wct.bgrid_slice(grid, x)
     assert torch.equal(wct.bgrid_slice(grid, x), got), "two calls differ"
     for off in (1, 2, 3):
