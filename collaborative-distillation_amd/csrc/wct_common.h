@@ -173,6 +173,15 @@ __attribute__((visibility("hidden"))) hipError_t launch_bgrid_fit(const float* c
                                                                   int smooth, float* grid, double* ws, size_t ws_bytes, hipStream_t s);
 __attribute__((visibility("hidden"))) hipError_t launch_bgrid_slice(const float* grid, int gz, int gh, int gw, const float* content, int H, int W,
                                                                     float* out_planar, uint8_t* out_hwc, int round_mode, bool use_lds, hipStream_t s);
+// ---- the device JPEG encoder (jpeg.hip; include/wct_hip_jpeg.h).  launch_jpeg_blocks: one launch.  launch_jpeg_pack: seven (eight with a
+// header, which is then written in front of the segment and counted in *len); `ws` (jpeg_workspace_bytes) and `stream` (jpeg_stream_bytes) are
+// the caller's scratch.  The grids are functions of (H, W) alone.
+__attribute__((visibility("hidden"))) long jpeg_num_blocks(int H, int W);
+__attribute__((visibility("hidden"))) size_t jpeg_workspace_bytes(long nb);
+__attribute__((visibility("hidden"))) size_t jpeg_stream_bytes(long nb);
+__attribute__((visibility("hidden"))) hipError_t launch_jpeg_blocks(const uint8_t* hwc, int H, int W, int quality, int16_t* coef, hipStream_t s);
+__attribute__((visibility("hidden"))) hipError_t launch_jpeg_pack(const int16_t* coef, int H, int W, const uint8_t* header, uint8_t* out,
+                                                                  uint64_t capacity, uint64_t* len, void* ws, void* stream, hipStream_t s);
 // ---- patch swap (swap.hip; include/wct_hip_swap.h).  launch_patch_match: the key norms, then one launch per chunk of `key_chunk` keys, then the
 // read-out; `run` (swap_run_bytes(Nq): the running (score, index) of every query) and `rnorm` (swap_norm_bytes(Nk)) are the caller's scratch; `sat`:
 // the context's saturation counter.  The number of launches is a function of (hs, ws, key_chunk) alone.

@@ -67,6 +67,10 @@ are looks) and sliced by the full content (wct_stylize_proxy; include/wct_hip_bg
 its edges; colour and tone are transferred, strokes are not.  One pair at a time (the serial loop); --alpha, --num_run, --transform,
 --content_size, --style_size and --round go with it, the other modes, --diversity, --preserve_color and --smooth_radius do not.  The files
 carry _proxy=<D> after the transform mark.
+--device_jpeg (not in the reference; off by default) encodes every .jpg / .jpeg output on the GPU (wct_jpeg_encode;
+include/wct_hip_jpeg.h) and writes the bytes: the file Pillow would write, byte for byte, without the host encode, and in the pipelined
+loop with the compressed file instead of the image copied to the host.  Other extensions are saved by Pillow as before.
+--jpeg_quality Q (1 .. 100, default 75 = Pillow's default) applies to .jpg / .jpeg outputs on either encoder.
 Decoding/encoding files needs Pillow on the host (the reference's own dependency); the GPU library is mandatory: there
 is no CPU fallback.
 """
@@ -77,6 +81,7 @@ import collections
 import math
 import os
 import sys
+import threading
 import time
 from typing import List, Optional, Tuple
 
@@ -220,6 +225,12 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--proxy_eps", type=float, default=None,
                    help="with --proxy_scale: regulariser of the local fits towards the global one, relative to images in [0, 1] (default 1e-2)")
     p.add_argument("--proxy_smooth", type=int, default=None, help="with --proxy_scale: [1 2 1] blur passes over the grid's sums, 0 .. 4 (default 1)")
+    # not in the reference: the .jpg / .jpeg outputs encoded on the device (include/wct_hip_jpeg.h), byte-identical to Pillow's file
+    p.add_argument("--device_jpeg", action="store_true",
+                   help="encode every .jpg / .jpeg output on the GPU and write the bytes: the same file as Pillow's, without the host encode "
+                        "and with the compressed file instead of the image copied to the host (default: off, Pillow encodes)")
+    p.add_argument("--jpeg_quality", type=int, default=75, help="quality of the .jpg / .jpeg outputs, 1 .. 100, with and without --device_jpeg "
+                                                                "(default 75, Pillow's default)")
     return p
 
 
@@ -762,6 +773,41 @@ def check_proxy_args(args) -> None:
         raise ValueError("--proxy_smooth: 0 .. %d expected, got %r" % (BGRID_MAX_SMOOTH, args.proxy_smooth))
 
 
+def check_jpeg_args(args) -> None:
+    """--jpeg_quality applies to every .jpg / .jpeg output, on either encoder; --device_jpeg only chooses the encoder."""
+    q = getattr(args, "jpeg_quality", 75)
+    if not 1 <= q <= 100:
+        raise ValueError("--jpeg_quality: 1 .. 100 expected, got %r" % (q,))
+
+
+def is_jpeg_file(path: str) -> bool:
+    return path.lower().endswith((".jpg", ".jpeg"))
+
+
+def save_host_u8(args, array, path: str) -> None:
+    """Pillow's save of a uint8 H x W x 3 host array; a JPEG at --jpeg_quality (75, the default, is what save(path) alone writes)."""
+    from PIL import Image
+    if is_jpeg_file(path):
+        Image.fromarray(array).save(path, quality=getattr(args, "jpeg_quality", 75))
+    else:
+        Image.fromarray(array).save(path)
+
+
+def device_jpeg_wanted(args, path: str) -> bool:
+    return bool(getattr(args, "device_jpeg", False)) and is_jpeg_file(path)
+
+
+def save_u8(wct, args, out_dev, path: str) -> None:
+    """The one place a loop saves its uint8 H x W x 3 DEVICE result (synchronises): with --device_jpeg a .jpg / .jpeg output is encoded
+    on the device and its bytes are written; everything else is copied to the host and saved by Pillow as before."""
+    if device_jpeg_wanted(args, path):
+        data = wct.jpeg_encode(out_dev, args.jpeg_quality)
+        with open(path, "wb") as f:
+            f.write(data)
+    else:
+        save_host_u8(args, out_dev.cpu().numpy(), path)   # .cpu() syncs
+
+
 def run_proxy(args, wct, pairs, content_dir, style_dir, logprinter) -> Tuple[float, int]:
     """--proxy_scale: the reference's loop with wct_stylize_proxy in the cascade's place, one pair at a time; the uint8 conversion is
     fused into the slice.  Returns (total seconds, pairs)."""
@@ -899,10 +945,9 @@ def run_video(args, wct, jobs, content_dir, style_dir, logprinter) -> Tuple[floa
                 t0 = time.time()
                 c_f32 = _to_tensor(wct, c_u8, args.content_size)
                 _, hwc = clip.stylize(c_f32, args.alpha, u8=True, round_mode=args.round_mode)
-                out = hwc.cpu().numpy()   # .cpu() syncs
-                if wct.saturation_count(reset=True):
+                if wct.saturation_count(reset=True):   # syncs
                     logprinter("WARNING: f16x3 range exceeded in this frame: its result deviates from the fp32 reference")
-                Image.fromarray(out).save(out_name(args, imname))
+                save_u8(wct, args, hwc, out_name(args, imname))
                 dt = time.time() - t0
                 avg += dt
                 n += 1
@@ -1218,8 +1263,7 @@ def _run_jobs(args, wct, logprinter, jobs) -> float:
         t0 = time.time()
         c_f32 = _to_tensor(wct, c_u8, args.content_size) if job.content else None
         res = job.stylise(c_f32, extra)
-        out = _finish_u8(wct, args, res, c_f32).cpu().numpy()   # .cpu() syncs
-        Image.fromarray(out).save(job.out)
+        save_u8(wct, args, _finish_u8(wct, args, res, c_f32), job.out)   # syncs
         dt = time.time() - t0
         total += dt
         logprinter("Elapsed time is: %.4f seconds" % dt)
@@ -1263,8 +1307,7 @@ def run_serial(args, wct, pairs, content_dir, style_dir, logprinter) -> float:
                 s_u8 = _upload_u8(os.path.join(style_dir, sfile))
             res = _fp32_fallback(wct, args, logprinter, c_f32, s_u8)
             style_cache.pop(sfile, None)          # its cached statistics may carry the clamp too
-        out = _finish_u8(wct, args, res, c_f32).cpu().numpy()   # .cpu() syncs
-        Image.fromarray(out).save(out_name(args, imname))
+        save_u8(wct, args, _finish_u8(wct, args, res, c_f32), out_name(args, imname))   # syncs
         dt = time.time() - t0
         avg += dt
         logprinter("Elapsed time is: %.4f seconds" % dt)
@@ -1293,9 +1336,37 @@ def run_pipelined(args, wct, pairs, content_dir, style_dir, logprinter) -> float
     def decode(path):
         return torch.from_numpy(load_rgb_u8(path)).pin_memory()
 
+    copy_streams = threading.local()
+
+    def stage(rec, out_dev):
+        """What of a pair's result goes to the host behind its event: the image for Pillow, or -- a .jpg / .jpeg output with
+        --device_jpeg -- only the length of the file that the device encodes; the writer then copies exactly that many bytes."""
+        if device_jpeg_wanted(args, rec["path"]):
+            rec["jpeg_dev"], length = wct.jpeg_encode_async(out_dev, args.jpeg_quality)
+            rec["len_host"] = torch.zeros(1, dtype=torch.int64).pin_memory()
+            rec["len_host"].copy_(length, non_blocking=True)
+            rec["jpeg_keep"] = length
+        else:
+            rec["host"] = torch.empty(out_dev.shape, dtype=torch.uint8, pin_memory=True)
+            rec["host"].copy_(out_dev, non_blocking=True)
+
     def save(rec):
         rec["ev"].synchronize()
-        Image.fromarray(rec["host"].numpy()).save(rec["path"])
+        if "jpeg_dev" in rec:
+            n = int(rec["len_host"][0])
+            if n < 0:
+                raise RuntimeError("--device_jpeg: %s overflowed the encoder's own bound" % rec["path"])
+            if not hasattr(copy_streams, "s"):
+                copy_streams.s = torch.cuda.Stream()      # this writer's own: the copy must not queue behind the next pairs' cascades
+            host = torch.empty(n, dtype=torch.uint8, pin_memory=True)
+            with torch.cuda.stream(copy_streams.s):
+                host.copy_(rec["jpeg_dev"][:n], non_blocking=True)
+            copy_streams.s.synchronize()
+            with open(rec["path"], "wb") as f:
+                f.write(host.numpy().tobytes())
+            rec.pop("jpeg_dev")
+        else:
+            save_host_u8(args, rec["host"].numpy(), rec["path"])
         return time.time()
 
     match = getattr(args, "preserve_color", None) == "match"     # per-pair matched styles (wct_stylize_color): no statistics cache, style_dev is the cache
@@ -1338,7 +1409,7 @@ def run_pipelined(args, wct, pairs, content_dir, style_dir, logprinter) -> float
             if s_u8 is None:
                 s_u8 = _upload_u8(os.path.join(style_dir, sfile))
             res = _fp32_fallback(wct, args, logprinter, rec["c_f32"], s_u8)
-            rec["host"].copy_(_finish_u8(wct, args, res, rec["c_f32"]))
+            stage(rec, _finish_u8(wct, args, res, rec["c_f32"]))
             rec["ev"] = torch.cuda.Event()
             rec["ev"].record()
             # the reset above acknowledged EVERY clamp so far, also one inside a style_prepare of a discarded pair (index > i): statistics
@@ -1404,14 +1475,14 @@ def run_pipelined(args, wct, pairs, content_dir, style_dir, logprinter) -> float
                 s_f32 = None
                 res = wct.stylize_prepared(c_f32, args.alpha, args.num_run)
             out_dev = _finish_u8(wct, args, res, c_f32)
-            host = torch.empty(out_dev.shape, dtype=torch.uint8, pin_memory=True)
-            host.copy_(out_dev, non_blocking=True)
+            rec = {"i": i, "imname": imname, "path": out_name(args, imname), "sfile": sfile, "c_f32": c_f32, "keep": (out_dev, res, c_u8, s_f32)}
+            stage(rec, out_dev)
             flag_host = torch.zeros(1, dtype=torch.float64).pin_memory()
             flag_host.copy_(wct.range_flag(), non_blocking=True)
             ev = torch.cuda.Event()
             ev.record()
-            inflight.append({"i": i, "imname": imname, "path": out_name(args, imname), "host": host, "flag_host": flag_host, "ev": ev,
-                             "sfile": sfile, "c_f32": c_f32, "keep": (out_dev, res, c_u8, s_f32)})
+            rec.update(flag_host=flag_host, ev=ev)
+            inflight.append(rec)
         for w in writes:
             w.result()
     finally:
@@ -1484,6 +1555,7 @@ def main(argv: Optional[List[str]] = None) -> int:
     check_motion_args(args)
     check_diverse_args(args)
     check_proxy_args(args)
+    check_jpeg_args(args)
     os.makedirs(args.outf, exist_ok=True)
     logprinter = LogPrinter(args.debug, os.path.join(args.outf, "log_%s_%s.txt" % (args.log_mark, args.mode)))
     logprinter(sorted(vars(args).items()))

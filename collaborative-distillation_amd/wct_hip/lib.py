@@ -102,6 +102,13 @@ BGRID_MAX_XY, BGRID_MAX_Z, BGRID_MAX_SMOOTH = 256, 32, 4            # WCT_BGRID_
 BGRID_FIT_ROWS, BGRID_TILE_W, BGRID_TILE_H, BGRID_LDS_VERTICES = 64, 128, 8, 320   # WCT_BGRID_FIT_ROWS, WCT_BGRID_TILE_*, WCT_BGRID_LDS_VERTICES
 BGRID_CELL, BGRID_BINS, BGRID_EPS, BGRID_SMOOTH = 16, 8, 1e-2, 1    # WCT_BGRID_*: the command line's defaults
 
+# every symbol include/wct_hip_jpeg.h declares (the device JPEG encoder behind --device_jpeg); bound from the same libwct_hip.so
+SYMBOLS_JPEG = ["wct_jpeg_header", "wct_jpeg_bound", "wct_jpeg_blocks", "wct_jpeg_pack", "wct_jpeg_encode"]
+JPEG_HEADER_BYTES, JPEG_MAX_DIM, JPEG_BLOCK_MAX_BITS = 623, 65500, 1728   # WCT_JPEG_HEADER_BYTES, WCT_JPEG_MAX_DIM, WCT_JPEG_BLOCK_MAX_BITS
+JPEG_SEG_MCUS, JPEG_SCAN_TILE, JPEG_SCAN_CHUNK, JPEG_PACK_SPAN, JPEG_STUFF_CHUNK = 8, 256, 256, 64, 1024   # WCT_JPEG_*: the launchers' units
+JPEG_OVERFLOW = 0xFFFFFFFFFFFFFFFF                                  # WCT_JPEG_OVERFLOW
+JPEG_QUALITY = 75                                                   # Pillow's default, and the command line's
+
 
 class WctLayer(ctypes.Structure):
     _fields_ = [("cin", c_int), ("cout", c_int), ("pool_after", c_int), ("up_after", c_int),
@@ -280,6 +287,12 @@ def load() -> ctypes.CDLL:
     lib.wct_bgrid_fit.argtypes = [c_void_p, vp, vp, c_int, c_int, c_int, c_int, c_int, c_double, c_int, vp]
     lib.wct_bgrid_slice.argtypes = [c_void_p, vp, c_int, c_int, c_int, vp, c_int, c_int, vp, vp, c_int]
     lib.wct_stylize_proxy.argtypes = [c_void_p, vp, c_int, c_int, vp, c_int, c_int, c_float, c_int, c_int, c_int, c_int, c_double, c_int, vp, vp, c_int]
+    u8p, u16p, u64p = POINTER(ctypes.c_uint8), POINTER(ctypes.c_uint16), POINTER(ctypes.c_uint64)
+    lib.wct_jpeg_header.argtypes = [c_int, c_int, c_int, u8p, u16p, u16p]
+    lib.wct_jpeg_bound.argtypes = [c_int, c_int, u64p]
+    lib.wct_jpeg_blocks.argtypes = [c_void_p, vp, c_int, c_int, c_int, vp]
+    lib.wct_jpeg_pack.argtypes = [c_void_p, vp, c_int, c_int, vp, ctypes.c_uint64, vp]
+    lib.wct_jpeg_encode.argtypes = [c_void_p, vp, c_int, c_int, c_int, vp, ctypes.c_uint64, vp]
     lib.wct_set_transform.argtypes = [c_void_p, c_int]
     lib.wct_get_transform.argtypes = [c_void_p, ip]
     lib.wct_transform_solve.argtypes = [c_void_p, c_int, c_int, c_double, vp, vp, vp, c_double, vp, vp, ip]

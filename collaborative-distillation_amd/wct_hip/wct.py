@@ -1352,6 +1352,103 @@ class WCT:
             self._style_keep = s      # the side stream reads it asynchronously
         return out.view(H, W, 3) if u8 else out.view(1, 3, H, W)
 
+    # ------------------------------------------------------------------ device JPEG encoder (include/wct_hip_jpeg.h)
+    @staticmethod
+    def _jpeg_args(what: str, H: int, W: int, quality=None) -> None:
+        if not (1 <= int(H) <= _lib.JPEG_MAX_DIM and 1 <= int(W) <= _lib.JPEG_MAX_DIM):
+            raise ValueError("%s: %d x %d is outside 1 .. %d per axis" % (what, H, W, _lib.JPEG_MAX_DIM))
+        if quality is not None and (isinstance(quality, bool) or not isinstance(quality, (int, np.integer)) or not 1 <= quality <= 100):
+            raise ValueError("%s: quality must be an integer in 1 .. 100, got %r" % (what, quality))
+
+    @staticmethod
+    def jpeg_header(H: int, W: int, quality: int = _lib.JPEG_QUALITY):
+        """(the 623 header bytes SOI .. SOS, the scaled Y table, the scaled chroma table; tables as 8 x 8 uint16 in natural order) of an
+        H x W file at `quality` (wct_jpeg_header, host only)."""
+        WCT._jpeg_args("jpeg_header", H, W, quality)
+        hdr = (ctypes.c_uint8 * _lib.JPEG_HEADER_BYTES)()
+        qy, qc = (ctypes.c_uint16 * 64)(), (ctypes.c_uint16 * 64)()
+        if _lib.load().wct_jpeg_header(int(H), int(W), int(quality), hdr, qy, qc) != _lib.WCT_OK:
+            raise ValueError("jpeg_header: refused %d x %d at quality %r" % (H, W, quality))
+        return bytes(hdr), np.array(qy, dtype=np.uint16).reshape(8, 8), np.array(qc, dtype=np.uint16).reshape(8, 8)
+
+    @staticmethod
+    def jpeg_bound(H: int, W: int) -> int:
+        """A capacity that no H x W image can overflow, header included (wct_jpeg_bound, host only)."""
+        WCT._jpeg_args("jpeg_bound", H, W)
+        n = ctypes.c_uint64()
+        if _lib.load().wct_jpeg_bound(int(H), int(W), byref(n)) != _lib.WCT_OK:
+            raise ValueError("jpeg_bound: refused %d x %d" % (H, W))
+        return int(n.value)
+
+    @staticmethod
+    def jpeg_num_blocks(H: int, W: int) -> int:
+        return 6 * ((int(H) + 15) // 16) * ((int(W) + 15) // 16)
+
+    @torch.no_grad()
+    def jpeg_blocks(self, img_u8: torch.Tensor, quality: int = _lib.JPEG_QUALITY) -> torch.Tensor:
+        """The quantised coefficients of a uint8 H x W x 3 device image: int16 [blocks, 64], zig-zag order inside a block, blocks in
+        scan order -- per 16 x 16 MCU Y00 Y01 Y10 Y11 Cb Cr, MCUs row-major (wct_jpeg_blocks)."""
+        x = self._u8(img_u8)
+        H, W = int(x.shape[0]), int(x.shape[1])
+        self._jpeg_args("jpeg_blocks", H, W, quality)
+        coef = torch.empty((self.jpeg_num_blocks(H, W), 64), device=x.device, dtype=torch.int16)
+        self._stream()
+        self._chk(self._lib.wct_jpeg_blocks(self._ctx, x.data_ptr(), H, W, int(quality), coef.data_ptr()))
+        return coef
+
+    def _jpeg_out(self, what: str, device, capacity, out, length):
+        if out is None:
+            out = torch.empty(int(capacity), device=device, dtype=torch.uint8)
+        elif out.dtype != torch.uint8 or not out.is_contiguous() or out.device != device:
+            raise ValueError("%s: `out` must be a contiguous uint8 tensor on the context's device" % what)
+        if length is None:
+            length = torch.empty(1, device=device, dtype=torch.int64)
+        elif length.dtype != torch.int64 or length.numel() != 1 or length.device != device:
+            raise ValueError("%s: `length` must be a one-element int64 tensor on the context's device" % what)
+        return out, length
+
+    @torch.no_grad()
+    def jpeg_pack(self, coef: torch.Tensor, H: int, W: int, capacity: Optional[int] = None, out: Optional[torch.Tensor] = None,
+                  length: Optional[torch.Tensor] = None):
+        """The entropy-coded segment of jpeg_blocks' coefficients -- stuffed, padded, FF D9 behind it -- without synchronising
+        (wct_jpeg_pack): (uint8 device buffer, one-element int64 device tensor with the length; -1 = the capacity did not suffice)."""
+        self._jpeg_args("jpeg_pack", H, W)
+        if coef.dtype != torch.int16 or coef.numel() != 64 * self.jpeg_num_blocks(H, W):
+            raise ValueError("jpeg_pack: expected int16 [%d, 64] coefficients, got %s %s" % (self.jpeg_num_blocks(H, W), coef.dtype, tuple(coef.shape)))
+        c = coef.to(self.stats_device).contiguous()
+        out, length = self._jpeg_out("jpeg_pack", c.device, self.jpeg_bound(H, W) if capacity is None else capacity, out, length)
+        cap = out.numel() if capacity is None else min(int(capacity), out.numel())
+        self._stream()
+        self._chk(self._lib.wct_jpeg_pack(self._ctx, c.data_ptr(), int(H), int(W), out.data_ptr(), cap, length.data_ptr()))
+        return out, length
+
+    @torch.no_grad()
+    def jpeg_encode_async(self, img_u8: torch.Tensor, quality: int = _lib.JPEG_QUALITY, capacity: Optional[int] = None,
+                          out: Optional[torch.Tensor] = None, length: Optional[torch.Tensor] = None):
+        """The complete JPEG file of a uint8 H x W x 3 device image, byte-identical to Pillow's Image.fromarray(img).save(path,
+        quality=quality), enqueued on the current stream without synchronising (wct_jpeg_encode): (uint8 device buffer, one-element
+        int64 device tensor with the file's length; -1 = the capacity did not suffice and nothing was written beyond it).  The
+        default capacity is jpeg_bound(H, W); `out` / `length` reuse a caller's buffers."""
+        x = self._u8(img_u8)
+        H, W = int(x.shape[0]), int(x.shape[1])
+        self._jpeg_args("jpeg_encode", H, W, quality)
+        out, length = self._jpeg_out("jpeg_encode", x.device, self.jpeg_bound(H, W) if capacity is None else capacity, out, length)
+        cap = out.numel() if capacity is None else min(int(capacity), out.numel())
+        self._stream()
+        self._chk(self._lib.wct_jpeg_encode(self._ctx, x.data_ptr(), H, W, int(quality), out.data_ptr(), cap, length.data_ptr()))
+        return out, length
+
+    def jpeg_encode(self, img_u8: torch.Tensor, quality: int = _lib.JPEG_QUALITY) -> bytes:
+        """jpeg_encode_async, then the file's bytes on the host (synchronises: for convenience and for tests).  The first attempt
+        uses a capacity of the raw image's size; one that overflows is repeated at jpeg_bound."""
+        H, W = int(img_u8.shape[0]), int(img_u8.shape[1])
+        for cap in (min(3 * H * W + 4096, self.jpeg_bound(H, W)), self.jpeg_bound(H, W)):
+            buf, length = self.jpeg_encode_async(img_u8, quality, capacity=cap)
+            n = int(length.item())
+            if n >= 0:
+                return buf[:n].cpu().numpy().tobytes()
+        raise _lib.WctError(_lib.WCT_ERR_STATE, "jpeg_encode: %d x %d overflowed its own bound" % (H, W))
+
     # ------------------------------------------------------------------ video mode (include/wct_hip_video.h)
     def clip(self, H: int, W: int, rate: float = _lib.CLIP_RATE, cut: float = _lib.CLIP_CUT, blend: float = _lib.CLIP_BLEND,
              sigma: float = _lib.CLIP_SIGMA, radius: int = _lib.CLIP_RADIUS, motion=None) -> "Clip":
