@@ -41,6 +41,13 @@
  * written as v - 1 in n bits, ZRL for runs above 15, EOB when the last coefficient is zero, one predictor per component over the whole
  * scan.  Blocks in scan order: per MCU Y00 Y01 Y10 Y11 Cb Cr, MCUs row-major.
  *
+ * Domain of the coder.  The segment is baseline JPEG when |DC difference| <= 2047 and |AC| <= 1023 in every block: the categories the
+ * tables have codes for, and all that wct_jpeg_blocks produces.  wct_jpeg_pack takes any int16 from its caller.  Outside the domain the
+ * category n is capped at 11 (DC) or 10 (AC), the symbol is formed with the capped n, and the low n bits of v (of v - 1 for a negative
+ * v) are written behind its code; v is the 32-bit DC difference or the AC coefficient.  Such a segment is not a valid file -- a decoder
+ * reads other values from it -- but it is deterministic, a function of the coefficients alone, and the call is memory safe: a block has
+ * at most WCT_JPEG_BLOCK_MAX_BITS bits whatever its coefficients, so the segment stays within wct_jpeg_bound.
+ *
  * Tail.  The bits are padded with 1-bits to a byte; 00 follows every FF byte, the padded last byte included; FF D9 ends the file.
  *
  * Header (WCT_JPEG_HEADER_BYTES = 623).  SOI; APP0 "JFIF\0", version 1.01, units 0, density 1 x 1, no thumbnail; DQT 0, DQT 1, each in
@@ -93,7 +100,10 @@ int wct_jpeg_bound(int H, int W, uint64_t* bytes);
 int wct_jpeg_blocks(wct_ctx* ctx, const uint8_t* hwc, int H, int W, int quality, int16_t* coef);
 /* out[0 .. *len) = the entropy-coded segment of the coefficients: stuffed, padded, followed by FF D9; *len (a DEVICE uint64) its
  * length.  When capacity does not suffice nothing at or beyond out + capacity is written and *len = WCT_JPEG_OVERFLOW: the length
- * slot is the status, the host sees it with the length.  WCT_ERR_INVALID: NULL, H or W out of range, a misaligned coef or len. */
+ * slot is the status, the host sees it with the length.  coef may hold any int16: baseline JPEG for |DC difference| <= 2047 and
+ * |AC| <= 1023, the capped categories of "Domain of the coder" above otherwise -- never more than WCT_JPEG_BLOCK_MAX_BITS a block, so
+ * wct_jpeg_bound(H, W) - WCT_JPEG_HEADER_BYTES suffices as a capacity for every input.  WCT_ERR_INVALID: NULL, H or W out of range, a
+ * misaligned coef or len. */
 int wct_jpeg_pack(wct_ctx* ctx, const int16_t* coef, int H, int W, uint8_t* out, uint64_t capacity, uint64_t* len);
 /* The complete file image: wct_jpeg_header, then wct_jpeg_pack of wct_jpeg_blocks (the coefficients in the context's scratch);
  * bit-identical to that composition.  *len counts the header.  Overflow and refusals as above. */

@@ -1,4 +1,4 @@
-"""The inputs of the device JPEG encoder's tests beyond the 15 cases of tests/jpeg_oracle.py: the sizes at the launchers' edges, read off
+"""The inputs of the device JPEG encoder's tests beyond the cases of tests/jpeg_oracle.py: the sizes at the launchers' edges, read off
 the constants of include/wct_hip_jpeg.h, and the committed seed whose padded last byte is FF.  tests/test_jpeg_cpu.py checks that each
 case is on the side of its edge that it claims; tests/test_jpeg_gpu.py runs them."""
 from wct_hip import lib as _lib

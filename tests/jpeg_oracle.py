@@ -1,7 +1,8 @@
 """numpy restatement of the device JPEG encoder's definition (include/wct_hip_jpeg.h): baseline, 8 bit, 4:2:0, standard Huffman
 tables -- what Pillow's Image.fromarray(rgb).save(path, quality=q) writes.  The transform is vectorised over blocks; the entropy
 coder walks them.  encode(rgb, quality) -> (coefficients int16 [blocks, 64] in zig-zag order, blocks in scan order; the file's bytes).
-tests/test_jpeg_cpu.py holds the bytes against Pillow, tests/test_jpeg_gpu.py the library against both."""
+tests/test_jpeg_cpu.py holds the bytes against Pillow, tests/test_jpeg_gpu.py the library against both.  walk() is the coder on its own,
+with wct_jpeg_pack's rule for coefficients outside baseline JPEG behind cap=True (tests/test_jpeg_pack_cpu.py, tests/test_jpeg_pack_gpu.py)."""
 import numpy as np
 
 ZIGZAG = np.array([0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
@@ -130,49 +131,72 @@ def coefficients(rgb, quality):
     return q[..., ZIGZAG].reshape(MH * MW * 6, 64).astype(np.int16)
 
 
-def bitstring(coef):
-    """The Huffman-coded bits of [blocks, 64] coefficients as a string of 0 / 1, before padding."""
-    parts = []
+DC_MAX_CATEGORY, AC_MAX_CATEGORY = 11, 10      # all that baseline JPEG has codes for: |DC difference| <= 2047, |AC| <= 1023
 
-    def put(code, length):
-        parts.append(format(code, "0%db" % length))
 
-    def value(v, n):
-        if n:
-            put(v if v >= 0 else (v - 1) & ((1 << n) - 1), n)
+def walk(coef, cap=False):
+    """What the coder emits for [blocks, 64] coefficients, in order: (block, table, "dc" or "ac", symbol, value bits, their number).
+    The pack is baseline JPEG on |DC difference| <= 2047 and |AC| <= 1023.  cap=False: anything else raises ValueError.  cap=True: what
+    wct_jpeg_pack defines there (include/wct_hip_jpeg.h) -- the category is capped at 11 (DC) or 10 (AC) and the low n bits of v, or of
+    v - 1 for a negative v, are written."""
+    def sized(v, most, b, what):
+        n = abs(v).bit_length()
+        if n > most:
+            if not cap:
+                raise ValueError("block %d: %s %d needs category %d; baseline JPEG has codes up to %d (cap=True applies wct_jpeg_pack's "
+                                 "rule for such input)" % (b, what, v, n, most))
+            n = most
+        return n, (v if v >= 0 else v - 1) & ((1 << n) - 1)
 
     pred = [0, 0, 0]
-    for b, zz in enumerate(coef.astype(np.int64).tolist()):
+    for b, zz in enumerate(np.asarray(coef).astype(np.int64).tolist()):
         k = b % 6
         comp, t = (0, 0) if k < 4 else (k - 3, 1)
         diff = zz[0] - pred[comp]
         pred[comp] = zz[0]
-        n = abs(diff).bit_length()
-        put(*DC_CODES[t][n])
-        value(diff, n)
+        n, bits = sized(diff, DC_MAX_CATEGORY, b, "DC difference")
+        yield b, t, "dc", n, bits, n
         run = 0
         for v in zz[1:]:
             if v == 0:
                 run += 1
                 continue
             while run > 15:
-                put(*AC_CODES[t][0xF0])
+                yield b, t, "ac", 0xF0, 0, 0
                 run -= 16
-            n = abs(v).bit_length()
-            put(*AC_CODES[t][run << 4 | n])
-            value(v, n)
+            n, bits = sized(v, AC_MAX_CATEGORY, b, "AC coefficient")
+            yield b, t, "ac", run << 4 | n, bits, n
             run = 0
         if run:
-            put(*AC_CODES[t][0x00])
+            yield b, t, "ac", 0x00, 0, 0
+
+
+def bitstring(coef, cap=False, starts=None):
+    """The Huffman-coded bits of [blocks, 64] coefficients as a string of 0 / 1, before padding.  cap: see walk().  starts: a list that
+    receives the bit offset of every block."""
+    parts, at, last = [], 0, -1
+    for b, t, kind, symbol, bits, n in walk(coef, cap):
+        if b != last and starts is not None:
+            starts.append(at)
+        last = b
+        code, length = (DC_CODES if kind == "dc" else AC_CODES)[t][symbol]
+        parts.append(format(code, "0%db" % length))
+        if n:
+            parts.append(format(bits, "0%db" % n))
+        at += length + n
     return "".join(parts)
 
 
-def entropy(coef):
-    """The entropy-coded segment of [blocks, 64] coefficients: stuffed, padded with ones, followed by FF D9."""
-    bits = bitstring(coef)
+def padded_stream(coef, cap=False):
+    """The bytes of the bits, padded with ones to a byte: what the stuffing reads."""
+    bits = bitstring(coef, cap)
     bits += "1" * (-len(bits) % 8)
-    raw = int(bits, 2).to_bytes(len(bits) // 8, "big")
-    return raw.replace(b"\xff", b"\xff\x00") + b"\xff\xd9"
+    return int(bits, 2).to_bytes(len(bits) // 8, "big") if bits else b""
+
+
+def entropy(coef, cap=False):
+    """The entropy-coded segment of [blocks, 64] coefficients: stuffed, padded with ones, followed by FF D9.  cap: see walk()."""
+    return padded_stream(coef, cap).replace(b"\xff", b"\xff\x00") + b"\xff\xd9"
 
 
 def encode(rgb, quality=75):
@@ -185,15 +209,26 @@ def encode(rgb, quality=75):
 CASES = [(1, 1, 75, "noise"), (8, 250, 75, "noise"), (23, 47, 30, "noise"), (18, 34, 75, "noise"), (16, 16, 75, "noise"), (41, 70, 90, "noise"),
          (9, 7, 50, "noise"), (24, 40, 95, "noise"), (33, 50, 1, "noise"), (64, 64, 100, "noise"),
          (130, 15, 85, "smooth"), (32, 48, 75, "smooth"), (37, 29, 75, "smooth"), (50, 33, 20, "smooth"), (17, 17, 75, "sat")]
+# and three that carry the largest categories through the transform and Pillow (tests/test_jpeg_pack_cpu.py says what they reach)
+CASES += [(40, 72, 100, "extremes"), (27, 90, 1, "extremes"), (35, 52, 100, "sat")]
 
 
 def make_image(H, W, kind, seed=0):
-    """uniform noise, smooth ramps with a sine, or random 0 / 255."""
+    """uniform noise, smooth ramps with a sine, random 0 / 255, or "extremes": left of the 16-aligned column nearest W / 2 an 8 x 8 chequer
+    of black and white (at quality 100 the Y DC alternates between -1024 and +1016), right of it a 16 x 16 chequer of (0, 0, 255) and
+    (255, 255, 0) (Cb is 255 and 0 there, so the Cb DC makes the same step from MCU to MCU)."""
     rng = np.random.default_rng([seed, H, W])
     if kind == "noise":
         return rng.integers(0, 256, (H, W, 3), dtype=np.uint8)
     if kind == "sat":
         return (rng.integers(0, 2, (H, W, 3)) * 255).astype(np.uint8)
+    if kind == "extremes":
+        yy, xx = np.mgrid[0:H, 0:W]
+        split = (W // 2 + 8) // 16 * 16
+        grey = ((yy // 8 + xx // 8) % 2 * 255)[..., None].repeat(3, 2)
+        odd = ((yy // 16 + xx // 16) % 2)[..., None]
+        colour = np.where(odd, np.array([255, 255, 0]), np.array([0, 0, 255]))
+        return np.where((xx < split)[..., None], grey, colour).astype(np.uint8)
     yy, xx = np.mgrid[0:H, 0:W]
     return np.stack([(yy * 5 + xx * 3) % 256, (xx * 7) % 256, (yy * 11 + 40 * np.sin(xx / 3.0)) % 256], -1).astype(np.uint8)
 

@@ -1,5 +1,5 @@
 """The device JPEG encoder on the GPU (include/wct_hip_jpeg.h): the coefficients against the numpy oracle and the file against Pillow,
-byte for byte -- on the 15 cases the definition was checked on, on inputs that reach the coder's other branches, and at every edge of
+byte for byte -- on the cases the definition was checked on, on inputs that reach the coder's other branches, and at every edge of
 the launchers; then what the entries promise about composition, overflow, views, graph replay and call history, and the command line."""
 import ctypes
 import os
