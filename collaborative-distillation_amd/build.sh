@@ -5,8 +5,8 @@
 #   WCT_DEFS="-DWCT_SP_TIMING" build.sh -f     instrumented builds (tools/experiments/*.sh)
 set -e
 cd "$(dirname "$0")"
-SRC="conv3x3 conv3x3_f16 conv3x3_sp level1 moments solve misc transform rotate noise color smooth swap attn scale resize bgrid regions cluster blend video motion wct_api api_model api_sharded api_image api_multi api_swap api_attn api_video api_motion api_diverse api_bgrid jpeg api_jpeg"
-HDR="csrc/wct_common.h csrc/conv_f16_dev.h csrc/mm_f64_dev.h csrc/philox_dev.h csrc/wct_ctx.h csrc/wct_clip.h ../include/wct_hip.h ../include/wct_hip_color.h ../include/wct_hip_guided.h ../include/wct_hip_scale.h ../include/wct_hip_smooth.h ../include/wct_hip_swap.h ../include/wct_hip_attn.h ../include/wct_hip_transform.h ../include/wct_hip_video.h ../include/wct_hip_motion.h ../include/wct_hip_diverse.h ../include/wct_hip_bgrid.h ../include/wct_hip_jpeg.h csrc/jpeg_tables.h build.sh"
+SRC="conv3x3 conv3x3_f16 conv3x3_sp level1 moments solve misc transform rotate noise color smooth swap attn scale resize bgrid regions cluster blend video motion wct_api api_model api_sharded api_image api_multi api_swap api_attn api_video api_motion api_diverse api_bgrid jpeg api_jpeg jdec api_jdec"
+HDR="csrc/wct_common.h csrc/conv_f16_dev.h csrc/mm_f64_dev.h csrc/philox_dev.h csrc/wct_ctx.h csrc/wct_clip.h ../include/wct_hip.h ../include/wct_hip_color.h ../include/wct_hip_guided.h ../include/wct_hip_scale.h ../include/wct_hip_smooth.h ../include/wct_hip_swap.h ../include/wct_hip_attn.h ../include/wct_hip_transform.h ../include/wct_hip_video.h ../include/wct_hip_motion.h ../include/wct_hip_diverse.h ../include/wct_hip_bgrid.h ../include/wct_hip_jpeg.h csrc/jpeg_tables.h ../include/wct_hip_jdec.h csrc/jdec_parse.h build.sh"
 OUT=${WCT_OUT:-libwct_hip.so}
 OBJ=build/obj${WCT_DEFS:+_$(echo "$WCT_DEFS" | md5sum | cut -c1-8)}
 mkdir -p "$OBJ"

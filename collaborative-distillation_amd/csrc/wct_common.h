@@ -182,6 +182,16 @@ __attribute__((visibility("hidden"))) size_t jpeg_stream_bytes(long nb);
 __attribute__((visibility("hidden"))) hipError_t launch_jpeg_blocks(const uint8_t* hwc, int H, int W, int quality, int16_t* coef, hipStream_t s);
 __attribute__((visibility("hidden"))) hipError_t launch_jpeg_pack(const int16_t* coef, int H, int W, const uint8_t* header, uint8_t* out,
                                                                   uint64_t capacity, uint64_t* len, void* ws, void* stream, hipStream_t s);
+// ---- the device JPEG decoder (jdec.hip; include/wct_hip_jdec.h).  `f` has passed wct_jdec::info_ok.  launch_jdec_coefficients: the unstuffing,
+// WCT_JDEC_LAUNCHES launches of the synchronisation, the count's scan, the write pass and the DC sums; `ws` (jdec_workspace_bytes) and `stream`
+// (jdec_stream_bytes) are the caller's scratch.  launch_jdec_pixels: two launches; `planes` (jdec_planes_bytes) the caller's scratch.
+struct wct_jdec_info;
+__attribute__((visibility("hidden"))) size_t jdec_stream_bytes(size_t n);
+__attribute__((visibility("hidden"))) size_t jdec_workspace_bytes(size_t n, const wct_jdec_info& f);
+__attribute__((visibility("hidden"))) size_t jdec_planes_bytes(const wct_jdec_info& f);
+__attribute__((visibility("hidden"))) hipError_t launch_jdec_coefficients(const uint8_t* scan, const wct_jdec_info& f, int rounds, int16_t* coef,
+                                                                          uint32_t* status, void* ws, void* stream, hipStream_t s);
+__attribute__((visibility("hidden"))) hipError_t launch_jdec_pixels(const int16_t* coef, const wct_jdec_info& f, uint8_t* hwc, void* planes, hipStream_t s);
 // ---- patch swap (swap.hip; include/wct_hip_swap.h).  launch_patch_match: the key norms, then one launch per chunk of `key_chunk` keys, then the
 // read-out; `run` (swap_run_bytes(Nq): the running (score, index) of every query) and `rnorm` (swap_norm_bytes(Nk)) are the caller's scratch; `sat`:
 // the context's saturation counter.  The number of launches is a function of (hs, ws, key_chunk) alone.

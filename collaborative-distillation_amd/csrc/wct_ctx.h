@@ -122,6 +122,9 @@ struct wct_ctx {
   // the device JPEG encoder (include/wct_hip_jpeg.h): the coefficients of wct_jpeg_encode, the blocks' bit offsets and the scans' partial sums,
   // and the unstuffed stream
   DevBuf jpCoef, jpWs, jpStream;
+  // the device JPEG decoder (include/wct_hip_jdec.h): the coefficients of wct_jdec_decode, the unstuffing's counts with the anchors, states,
+  // block offsets and DC partial sums, the compacted stream, and the component planes of wct_jdec_pixels
+  DevBuf jdCoef, jdWs, jdStream, jdPlanes;
   int bgrid_lds = 1;   // debug key "bgrid_lds": 0 = the slice reads every tile's vertices from global memory (same bits)
   // patch swap (include/wct_hip_swap.h): the two encoded features, the two projected maps, the blended feature, the indices, the running
   // (score, index) of every query between the key chunks' launches, the key norms, and the all-zero label map of the one-label affine apply
@@ -228,7 +231,7 @@ struct wct_ctx {
                       &shIn, &shOut, &shNext, &shEdge, &shStyle, &shStats, &shMb,
                       &regLab, &regHist, &regSums, &regMb, &regFeat, &wsRegMom, &wsRegApply,
                       &blendW, &blendStat, &wsBlendPool, &wsBlendApply, &gdLab, &gdHist, &kmFeatC, &kmFeatS, &kmWs, &kmStat, &motionWs, &dvWs, &dvZ,
-                      &bgWs, &bgGrid, &pxCl, &pxSl, &jpCoef, &jpWs, &jpStream})
+                      &bgWs, &bgGrid, &pxCl, &pxSl, &jpCoef, &jpWs, &jpStream, &jdCoef, &jdWs, &jdStream, &jdPlanes})
       f(*b, &main, true);
     for (DevBuf* b : {&gdSums, &wsGdMom}) f(*b, &side, true);   // the guided call's style side
     for (DevBuf& b : scF) f(b, &main, true);

@@ -71,6 +71,10 @@ carry _proxy=<D> after the transform mark.
 include/wct_hip_jpeg.h) and writes the bytes: the file Pillow would write, byte for byte, without the host encode, and in the pipelined
 loop with the compressed file instead of the image copied to the host.  Other extensions are saved by Pillow as before.
 --jpeg_quality Q (1 .. 100, default 75 = Pillow's default) applies to .jpg / .jpeg outputs on either encoder.
+--device_decode (not in the reference; off by default) decodes every .jpg / .jpeg input on the GPU (wct_jdec_decode;
+include/wct_hip_jdec.h): the pixels Pillow would give, value for value, with the file's entropy-coded segment instead of the image
+copied to the device.  A file the device decoder does not take (progressive, CMYK, ...) or does not finish (status UNSYNC / CORRUPT) is
+decoded by Pillow as before, logged once per file; nothing is ever computed from bad pixels.  Masks, weight maps and PNGs are untouched.
 Decoding/encoding files needs Pillow on the host (the reference's own dependency); the GPU library is mandatory: there
 is no CPU fallback.
 """
@@ -229,6 +233,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--device_jpeg", action="store_true",
                    help="encode every .jpg / .jpeg output on the GPU and write the bytes: the same file as Pillow's, without the host encode "
                         "and with the compressed file instead of the image copied to the host (default: off, Pillow encodes)")
+    # not in the reference: the .jpg / .jpeg inputs decoded on the device (include/wct_hip_jdec.h), pixel-identical to Pillow's decode
+    p.add_argument("--device_decode", action="store_true",
+                   help="decode every baseline .jpg / .jpeg input on the GPU: the same pixels as Pillow's, with the compressed segment instead "
+                        "of the image copied to the device; other files fall back to Pillow (default: off, Pillow decodes)")
     p.add_argument("--jpeg_quality", type=int, default=75, help="quality of the .jpg / .jpeg outputs, 1 .. 100, with and without --device_jpeg "
                                                                 "(default 75, Pillow's default)")
     return p
@@ -1225,9 +1233,69 @@ def _on_device(array, pin=False):
     return t.pin_memory().cuda(non_blocking=True) if pin else t.cuda()
 
 
+# --device_decode: the decoder of the running main(), set once its engine exists and cleared in main()'s finally (None: Pillow decodes
+# everything); _upload_u8, which its many callers give a path and nothing else, and run_pipelined's decode ask it
+_DEVICE_DECODER = None
+
+
+class DeviceDecoder:
+    """The host side of --device_decode.  read(path), in any thread: (info, pinned segment) of a .jpg / .jpeg file the device decoder
+    takes; Pillow's uint8 H x W x 3 array, decoded from the bytes already read, of one it does not take (logged once per file); None
+    for any other file and for one the device has refused before.  enqueue(item), in the main thread: the uint8 H x W x 3 device
+    image and a pinned status word that is valid once the stream has passed this point."""
+    STATUS = {1: "the synchronisation did not converge (status UNSYNC)", 2: "the scan is not what its header promises (status CORRUPT)"}
+
+    def __init__(self, wct, logprinter):
+        self.wct, self.log = wct, logprinter
+        self.host_only = set()
+        self.lock = threading.Lock()
+
+    def refuse(self, path, why):
+        with self.lock:
+            if path not in self.host_only:
+                self.host_only.add(path)
+                self.log("--device_decode: %s: %s; Pillow decodes it" % (path, why))
+
+    def read(self, path):
+        import io
+        import numpy as np
+        import torch
+        from PIL import Image
+        if not is_jpeg_file(path) or path in self.host_only:
+            return None
+        with open(path, "rb") as f:
+            data = f.read()
+        info = self.wct.jdec_parse(data)
+        if info is None or not info.scan_length:
+            self.refuse(path, "not a baseline file the device decoder takes")
+            return np.array(Image.open(io.BytesIO(data)).convert("RGB"), dtype=np.uint8)     # load_rgb_u8 of the same bytes
+        seg = np.frombuffer(data, np.uint8, int(info.scan_length), int(info.scan_offset)).copy()
+        return info, torch.from_numpy(seg).pin_memory()
+
+    def enqueue(self, item):
+        import torch
+        info, seg = item
+        out, status = self.wct.jdec_decode_async(seg.cuda(non_blocking=True), info)
+        host = torch.zeros(1, dtype=torch.int32).pin_memory()
+        host.copy_(status, non_blocking=True)
+        return out, host
+
+
 def _upload_u8(path):
     """Decode `path` to uint8 HWC and send it off to the device: a decoded frame crosses PCIe as it is (3 B/px, pinned); Resize and
-    ToTensor run on the GPU."""
+    ToTensor run on the GPU.  With --device_decode a baseline .jpg / .jpeg file crosses as its compressed segment and is decoded
+    there (synchronises for the status: a file the device does not finish is decoded by Pillow)."""
+    d = _DEVICE_DECODER
+    item = d.read(path) if d is not None else None
+    if item is not None and not isinstance(item, tuple):
+        return _on_device(item, pin=True)
+    if item is not None:
+        import torch
+        out, host = d.enqueue(item)
+        torch.cuda.current_stream().synchronize()
+        if int(host[0]) == 0:
+            return out
+        d.refuse(path, d.STATUS.get(int(host[0]), "status %d" % int(host[0])))
     return _on_device(load_rgb_u8(path), pin=True)
 
 
@@ -1333,8 +1401,22 @@ def run_pipelined(args, wct, pairs, content_dir, style_dir, logprinter) -> float
     dec = cf.ThreadPoolExecutor(io, thread_name_prefix="wct-decode")
     wr = cf.ThreadPoolExecutor(io, thread_name_prefix="wct-write")
 
+    jdec = _DEVICE_DECODER
+
     def decode(path):
-        return torch.from_numpy(load_rgb_u8(path)).pin_memory()
+        """Pool thread: the pinned image, or -- --device_decode, a file the device takes -- its parsed header and pinned segment."""
+        item = jdec.read(path) if jdec is not None else None
+        if isinstance(item, tuple):
+            return item
+        return torch.from_numpy(item if item is not None else load_rgb_u8(path)).pin_memory()
+
+    def upload(item, path, pending):
+        """Main thread: the uint8 device image of what decode() returned; a device decode leaves (path, pinned status) in `pending`."""
+        if isinstance(item, tuple):
+            out, host = jdec.enqueue(item)
+            pending.append((path, host))
+            return out
+        return item.cuda(non_blocking=True)
 
     copy_streams = threading.local()
 
@@ -1398,6 +1480,22 @@ def run_pipelined(args, wct, pairs, content_dir, style_dir, logprinter) -> float
         """Pair leaves the window: its flag has been copied with its image."""
         nonlocal last_flag, nxt, done_log
         rec["ev"].synchronize()
+        bad = [(p, int(h[0])) for p, h in rec["jdec"] if int(h[0]) != 0]
+        if bad:
+            # the device did not finish one of this pair's files: nothing computed from it may be written.  Like a clamped pair, drop
+            # what was enqueued behind it and the statistics prepared since; the pair itself is redone from Pillow's decode
+            torch.cuda.synchronize()
+            inflight.clear()
+            for p, st in bad:
+                jdec.refuse(p, jdec.STATUS.get(st, "status %d" % st))
+            for f in [f for f, by in style_by.items() if by >= rec["i"]] + [rec["sfile"]]:
+                style_cache.pop(f, None)
+                style_dev.pop(f, None)
+                style_by.pop(f, None)
+            fut.clear()
+            last_flag = float(wct.range_flag().reshape(-1)[0].item())   # a clamp of a dropped pair is dropped with it
+            nxt = rec["i"]
+            return
         flag = float(rec["flag_host"][0])
         if flag > last_flag:
             # clamped: redo this pair in fp32, drop what was enqueued behind it (same statistics objects) and resume after it
@@ -1448,16 +1546,17 @@ def run_pipelined(args, wct, pairs, content_dir, style_dir, logprinter) -> float
             cfile, sfile = pairs[i]
             imname = pair_name(cfile, sfile)
             logprinter("\n" + "*" * 30 + ' #%s: Transferring "%s"' % (i, imname))
-            c_u8 = fut[("c", cfile)].result().cuda(non_blocking=True)
+            pending = []
+            c_u8 = upload(fut[("c", cfile)].result(), os.path.join(content_dir, cfile), pending)
             if match:
                 s_u8 = style_dev.pop(sfile, None)
                 if s_u8 is None:
-                    s_u8 = fut[("s", sfile)].result().cuda(non_blocking=True)
+                    s_u8 = upload(fut[("s", sfile)].result(), os.path.join(style_dir, sfile), pending)
                 style_dev[sfile] = s_u8                     # (re-inserted: most recently used last)
                 while len(style_dev) > depth + 2:
                     style_dev.pop(next(iter(style_dev)))
             elif sfile not in style_cache:
-                s_u8 = fut[("s", sfile)].result().cuda(non_blocking=True)
+                s_u8 = upload(fut[("s", sfile)].result(), os.path.join(style_dir, sfile), pending)
                 style_dev[sfile] = s_u8
                 while len(style_dev) > depth + 2:           # the fallback reloads a style it no longer finds here: keep the few that can be in flight
                     style_dev.pop(next(iter(style_dev)))
@@ -1475,7 +1574,8 @@ def run_pipelined(args, wct, pairs, content_dir, style_dir, logprinter) -> float
                 s_f32 = None
                 res = wct.stylize_prepared(c_f32, args.alpha, args.num_run)
             out_dev = _finish_u8(wct, args, res, c_f32)
-            rec = {"i": i, "imname": imname, "path": out_name(args, imname), "sfile": sfile, "c_f32": c_f32, "keep": (out_dev, res, c_u8, s_f32)}
+            rec = {"i": i, "imname": imname, "path": out_name(args, imname), "sfile": sfile, "c_f32": c_f32, "keep": (out_dev, res, c_u8, s_f32),
+                   "jdec": pending}
             stage(rec, out_dev)
             flag_host = torch.zeros(1, dtype=torch.float64).pin_memory()
             flag_host.copy_(wct.range_flag(), non_blocking=True)
@@ -1556,6 +1656,16 @@ def main(argv: Optional[List[str]] = None) -> int:
     check_diverse_args(args)
     check_proxy_args(args)
     check_jpeg_args(args)
+    global _DEVICE_DECODER
+    try:
+        return _run(args)
+    finally:
+        _DEVICE_DECODER = None      # however the run ends: the decoder holds the engine
+
+
+def _run(args) -> int:
+    """main() behind its argument checks: the log, the engine, the mode's or the plain run's loop."""
+    global _DEVICE_DECODER
     os.makedirs(args.outf, exist_ok=True)
     logprinter = LogPrinter(args.debug, os.path.join(args.outf, "log_%s_%s.txt" % (args.log_mark, args.mode)))
     logprinter(sorted(vars(args).items()))
@@ -1568,6 +1678,7 @@ def main(argv: Optional[List[str]] = None) -> int:
         jobs = mode.jobs(args, content_dir, style_dir) if mode.early else None
         from .wct import WCT
         wct = WCT(args)
+        _DEVICE_DECODER = DeviceDecoder(wct, logprinter) if getattr(args, "device_decode", False) else None
         if mode.early:
             logprinter(mode.number(jobs))
         if args.pipeline > 0:
@@ -1583,6 +1694,7 @@ def main(argv: Optional[List[str]] = None) -> int:
 
     from .wct import WCT      # raises ImportError if libwct_hip.so is missing: no CPU fallback
     wct = WCT(args)
+    _DEVICE_DECODER = DeviceDecoder(wct, logprinter) if getattr(args, "device_decode", False) else None
     logprinter("Number of content-style pairs: %s" % len(pairs))
     if args.pipeline > 0:
         wall = run_pipelined(args, wct, pairs, content_dir, style_dir, logprinter)

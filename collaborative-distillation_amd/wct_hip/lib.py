@@ -109,6 +109,22 @@ JPEG_SEG_MCUS, JPEG_SCAN_TILE, JPEG_SCAN_CHUNK, JPEG_PACK_SPAN, JPEG_STUFF_CHUNK
 JPEG_OVERFLOW = 0xFFFFFFFFFFFFFFFF                                  # WCT_JPEG_OVERFLOW
 JPEG_QUALITY = 75                                                   # Pillow's default, and the command line's
 
+# every symbol include/wct_hip_jdec.h declares (the device JPEG decoder behind --device_decode); bound from the same libwct_hip.so
+SYMBOLS_JDEC = ["wct_jdec_parse", "wct_jdec_num_blocks", "wct_jdec_coefficients", "wct_jdec_pixels", "wct_jdec_decode"]
+JDEC_UNSUPPORTED = 1                                                # WCT_JDEC_UNSUPPORTED
+JDEC_STATUS_OK, JDEC_STATUS_UNSYNC, JDEC_STATUS_CORRUPT = 0, 1, 2   # WCT_JDEC_STATUS_*
+JDEC_SUBSEQ_BITS, JDEC_SYNC_THREADS, JDEC_LAUNCHES, JDEC_ROUNDS, JDEC_MAX_ROUNDS = 1024, 256, 4, 32, 4096   # WCT_JDEC_*: the schedule
+JDEC_CHUNK, JDEC_SCAN_CHUNK, JDEC_DC_TILE, JDEC_MAX_DIM, JDEC_MAX_SCAN_BYTES = 1024, 256, 256, 65500, 0x0FFFFFFF   # the launchers' units and the limits
+
+
+class WctJdecInfo(ctypes.Structure):
+    """include/wct_hip_jdec.h wct_jdec_info."""
+    _fields_ = [("H", ctypes.c_int32), ("W", ctypes.c_int32), ("ncomp", ctypes.c_int32), ("restart_interval", ctypes.c_int32),
+                ("hs", ctypes.c_int32 * 3), ("vs", ctypes.c_int32 * 3), ("tq", ctypes.c_int32 * 3), ("td", ctypes.c_int32 * 3),
+                ("ta", ctypes.c_int32 * 3), ("reserved", ctypes.c_int32), ("scan_offset", ctypes.c_uint64), ("scan_length", ctypes.c_uint64),
+                ("qt", (ctypes.c_uint8 * 64) * 4), ("dc_counts", (ctypes.c_uint8 * 16) * 2), ("dc_vals", (ctypes.c_uint8 * 16) * 2),
+                ("ac_counts", (ctypes.c_uint8 * 16) * 2), ("ac_vals", (ctypes.c_uint8 * 256) * 2)]
+
 
 class WctLayer(ctypes.Structure):
     _fields_ = [("cin", c_int), ("cout", c_int), ("pool_after", c_int), ("up_after", c_int),
@@ -293,6 +309,12 @@ def load() -> ctypes.CDLL:
     lib.wct_jpeg_blocks.argtypes = [c_void_p, vp, c_int, c_int, c_int, vp]
     lib.wct_jpeg_pack.argtypes = [c_void_p, vp, c_int, c_int, vp, ctypes.c_uint64, vp]
     lib.wct_jpeg_encode.argtypes = [c_void_p, vp, c_int, c_int, c_int, vp, ctypes.c_uint64, vp]
+    jip = POINTER(WctJdecInfo)
+    lib.wct_jdec_parse.argtypes = [c_void_p, c_size_t, jip]
+    lib.wct_jdec_num_blocks.argtypes = [jip, u64p]
+    lib.wct_jdec_coefficients.argtypes = [c_void_p, vp, jip, c_int, vp, vp]
+    lib.wct_jdec_pixels.argtypes = [c_void_p, vp, jip, vp]
+    lib.wct_jdec_decode.argtypes = [c_void_p, vp, jip, c_int, vp, vp]
     lib.wct_set_transform.argtypes = [c_void_p, c_int]
     lib.wct_get_transform.argtypes = [c_void_p, ip]
     lib.wct_transform_solve.argtypes = [c_void_p, c_int, c_int, c_double, vp, vp, vp, c_double, vp, vp, ip]

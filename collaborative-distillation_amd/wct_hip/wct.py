@@ -1449,6 +1449,94 @@ class WCT:
                 return buf[:n].cpu().numpy().tobytes()
         raise _lib.WctError(_lib.WCT_ERR_STATE, "jpeg_encode: %d x %d overflowed its own bound" % (H, W))
 
+    # ------------------------------------------------------------------ device JPEG decoder (include/wct_hip_jdec.h)
+    @staticmethod
+    def jdec_parse(data: bytes):
+        """The wct_jdec_info of a JPEG file's bytes (wct_jdec_parse, host only), or None when the file is not one the device decoder
+        takes (WCT_JDEC_UNSUPPORTED): progressive, CMYK, several scans, truncated, ..."""
+        buf = bytes(data)
+        info = _lib.WctJdecInfo()
+        rc = _lib.load().wct_jdec_parse(buf, len(buf), byref(info))
+        if rc == _lib.JDEC_UNSUPPORTED:
+            return None
+        if rc != _lib.WCT_OK:
+            raise ValueError("jdec_parse: refused (code %d)" % rc)
+        return info
+
+    @staticmethod
+    def jdec_num_blocks(info) -> int:
+        n = ctypes.c_uint64()
+        if _lib.load().wct_jdec_num_blocks(byref(info), byref(n)) != _lib.WCT_OK:
+            raise ValueError("jdec_num_blocks: not an info that jdec_parse fills")
+        return int(n.value)
+
+    def _jdec_scan(self, what: str, scan: torch.Tensor, info) -> torch.Tensor:
+        if scan.dtype != torch.uint8 or scan.dim() != 1 or not scan.is_contiguous() or scan.numel() < int(info.scan_length):
+            raise ValueError("%s: the segment must be a contiguous 1-D uint8 tensor of at least info.scan_length = %d bytes" % (what, info.scan_length))
+        return scan.to(self.stats_device)
+
+    @staticmethod
+    def _jdec_rounds(what: str, rounds) -> int:
+        if isinstance(rounds, bool) or not isinstance(rounds, int) or not 0 <= rounds <= _lib.JDEC_MAX_ROUNDS:
+            raise ValueError("%s: rounds 0 .. %d expected, got %r" % (what, _lib.JDEC_MAX_ROUNDS, rounds))
+        return rounds
+
+    @torch.no_grad()
+    def jdec_coefficients(self, scan: torch.Tensor, info, rounds: int = 0):
+        """The coefficients of a file's entropy-coded segment on the device (file[info.scan_offset:][:info.scan_length] as a uint8
+        tensor), without synchronising (wct_jdec_coefficients): (int16 [blocks, 64] in zig-zag order, blocks in scan order, DC absolute
+        -- the layout of jpeg_blocks; one-element int32 device tensor with the status JDEC_STATUS_*)."""
+        s = self._jdec_scan("jdec_coefficients", scan, info)
+        coef = torch.empty((self.jdec_num_blocks(info), 64), device=s.device, dtype=torch.int16)
+        status = torch.empty(1, device=s.device, dtype=torch.int32)
+        self._stream()
+        self._chk(self._lib.wct_jdec_coefficients(self._ctx, s.data_ptr(), byref(info), self._jdec_rounds("jdec_coefficients", rounds),
+                                                  coef.data_ptr(), status.data_ptr()))
+        return coef, status
+
+    @torch.no_grad()
+    def jdec_pixels(self, coef: torch.Tensor, info) -> torch.Tensor:
+        """uint8 H x W x 3 of jdec_coefficients' coefficients (wct_jdec_pixels): what Pillow's Image.open(path).convert("RGB") holds."""
+        if coef.dtype != torch.int16 or coef.numel() != 64 * self.jdec_num_blocks(info):
+            raise ValueError("jdec_pixels: expected int16 [%d, 64] coefficients, got %s %s" % (self.jdec_num_blocks(info), coef.dtype, tuple(coef.shape)))
+        c = coef.to(self.stats_device).contiguous()
+        out = torch.empty((int(info.H), int(info.W), 3), device=c.device, dtype=torch.uint8)
+        self._stream()
+        self._chk(self._lib.wct_jdec_pixels(self._ctx, c.data_ptr(), byref(info), out.data_ptr()))
+        return out
+
+    @torch.no_grad()
+    def jdec_decode_async(self, scan: torch.Tensor, info, rounds: int = 0, out: Optional[torch.Tensor] = None,
+                          status: Optional[torch.Tensor] = None):
+        """The pixels of a file's entropy-coded segment, enqueued on the current stream without synchronising (wct_jdec_decode):
+        (uint8 H x W x 3 device tensor, one-element int32 device tensor with the status).  Unless the status is JDEC_STATUS_OK the
+        pixels are not to be used.  `out` / `status` reuse a caller's buffers."""
+        s = self._jdec_scan("jdec_decode", scan, info)
+        H, W = int(info.H), int(info.W)
+        if out is None:
+            out = torch.empty((H, W, 3), device=s.device, dtype=torch.uint8)
+        elif out.dtype != torch.uint8 or tuple(out.shape) != (H, W, 3) or not out.is_contiguous() or out.device != s.device:
+            raise ValueError("jdec_decode: `out` must be a contiguous uint8 [%d, %d, 3] tensor on the context's device" % (H, W))
+        if status is None:
+            status = torch.empty(1, device=s.device, dtype=torch.int32)
+        elif status.dtype != torch.int32 or status.numel() != 1 or status.device != s.device:
+            raise ValueError("jdec_decode: `status` must be a one-element int32 tensor on the context's device")
+        self._stream()
+        self._chk(self._lib.wct_jdec_decode(self._ctx, s.data_ptr(), byref(info), self._jdec_rounds("jdec_decode", rounds), out.data_ptr(),
+                                            status.data_ptr()))
+        return out, status
+
+    def jdec_decode(self, data: bytes, rounds: int = 0):
+        """A JPEG file's bytes to (uint8 H x W x 3 device tensor, status), or None when jdec_parse does not take the file
+        (synchronises: for convenience and for tests)."""
+        info = self.jdec_parse(data)
+        if info is None:
+            return None
+        seg = np.frombuffer(data, np.uint8, int(info.scan_length), int(info.scan_offset))
+        scan = torch.from_numpy(seg.copy()).to(self.stats_device) if len(seg) else torch.zeros(0, dtype=torch.uint8, device=self.stats_device)
+        out, status = self.jdec_decode_async(scan, info, rounds)
+        return out, int(status.item())
+
     # ------------------------------------------------------------------ video mode (include/wct_hip_video.h)
     def clip(self, H: int, W: int, rate: float = _lib.CLIP_RATE, cut: float = _lib.CLIP_CUT, blend: float = _lib.CLIP_BLEND,
              sigma: float = _lib.CLIP_SIGMA, radius: int = _lib.CLIP_RADIUS, motion=None) -> "Clip":
